@@ -14,12 +14,23 @@ folds are minimum free energies (ADX_FOLD_MFE).
 reference's own scoring path; config 3 without the bppm term).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--walkers 4096] [--length 100] [--fold mfe|pf]
+                    [--dump-outputs DIR] [--full]
 
-The default (MFE) line also carries `sub_records` measured in the same run:
+A plain run sets up, warms up, times the K steps and prints one JSON line:
+value (MC steps/s), ms_per_step, the outcome counters.  `--dump-outputs DIR`
+also writes what the timed path left after its last step (Engine.download:
+the walkers' sequences, scores and counters) as DIR/<name>.npy; the walkers
+and their RNG streams are seeded by walker id, so two runs with the same
+arguments hold the same arrays.
+
+`--full` adds everything else to the line: the roofline of the dominant kernel
+(HIP events of the timed run, one traced step after it), a CPU baseline, and on
+the default (MFE) line `sub_records` measured in the same run:
 "pf" (the reference's own vrna_pf scoring path), "config3" (pf + bppm, N = 100)
 and "config4" (pf + bppm, N = 150, one GPU's shard), each with value,
 ms_per_step, the roofline of its dominant kernel (named from the engine's own
 dispatch, adx_last_kernel_names) and, for pf / config3, a CPU baseline.
+`--no-cpu-baseline` / `--no-sub-records` leave those legs out of a --full run.
 
 N > 1: one rank per GPU.  Under torch.distributed.run (WORLD_SIZE set) each
 process is one rank; a plain `python bench.py --gpus N` starts that launcher
@@ -57,9 +68,16 @@ def parse():
                     help="mfe = BASELINE configs[1] (default); pf = partition-function objective")
     ap.add_argument("--bppm", action="store_true",
                     help="configs 3/4: add apo/holo base-pair probability terms (outside pass; --fold pf)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: the roofline of the dominant kernel (one traced step "
+                         "after the timed region), the CPU baseline and, on the default (MFE) line, the "
+                         "PF / config 3 / config 4 sub-records")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the walkers' final sequences, scores and counters "
+                         "(what Engine.download returns) as DIR/<name>.npy")
     ap.add_argument("--cpu-seconds", type=float, default=15.0,
-                    help="approximate budget of the CPU-baseline sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="--full: approximate budget of the CPU-baseline sample")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--replica-interval", type=int, default=0,
                     help="BASELINE config 5: one temperature rung per rank (0.5*1.5^r), RCCL swap of "
                          "walker configurations between neighbouring rungs every K steps (N > 1 only)")
@@ -71,7 +89,7 @@ def parse():
                     help="each rank writes DIR/rank<r>.npz with its global walker ids and final sequences, "
                          "scores and counters (after the timed region; tests of G-independence)")
     ap.add_argument("--traffic-json", default=None,
-                    help="PMC summary (tools/pmc_traffic.py) of this workload, fills roofline.traffic "
+                    help="--full: PMC summary (tools/pmc_traffic.py) of this workload, fills roofline.traffic "
                          "(default profiles/traffic_latest_<fold>.json)")
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU: gloo ranks, a host sleep per step (tests the --gpus N launch path)")
@@ -81,9 +99,9 @@ def parse():
                     help="N > 1 rehearsal on one GPU: every rank runs its engine on device 0 "
                          "(use with --dist-backend gloo)")
     ap.add_argument("--no-sub-records", action="store_true",
-                    help="skip the PF / config 3 / config 4 sub-records of the default (MFE) run")
+                    help="--full without the PF / config 3 / config 4 sub-records of the default (MFE) run")
     ap.add_argument("--sub-steps-c4", type=int, default=60,
-                    help="timed steps of the config-4 sub-record (N = 150)")
+                    help="--full: timed steps of the config-4 sub-record (N = 150)")
     return ap.parse_args()
 
 
@@ -266,99 +284,28 @@ def executed_inside_work(eng, cur_seqs, tmpl, active, fold, sample=32):
     return (ex_sum / n if n else None), (full_sum / n if n else None), n
 
 
-def measure(a, fold, bppm, length, steps, warmup, rank, world, gids_rank, dist, dev, local_rank,
-            traffic_json=None, cpu=False, cpu_seconds=15.0, dump=None):
-    """Run one workload (W walkers of this rank) and return its record: value
-    (all ranks), ms_per_step, roofline of the dominant kernel, outcomes."""
-    from addapt_amd import native, roofline, shard, workloads
+def kernel_events(eng):
+    """HIP-event times and kernel names the engine recorded for its last run_steps."""
+    return (eng.last_kernel_ms(),               # whole timed run_steps (3 kernels per step)
+            eng.last_score_kernel_ms(),         # the step's score window, per launch (+ launches)
+            eng.last_kernel_split_ms(),         # the same window split per kernel
+            eng.last_kernel_names())            # what the engine launched
 
-    tmpl, active = workloads.synthetic(length)
-    terms = workloads.config_objective(length, bppm=bppm)
-    apt = (workloads.THEO_SEQ, workloads.THEO_FOLD, native.theo_energy())
-    replica_mode = a.replica_interval > 0 and world > 1
-    if replica_mode:
-        from addapt_amd import replica
 
-        temps = replica.ladder_temperatures(world)
-        th = native.make_thermostat("fixed", t=temps[rank])
-    else:
-        th = native.make_thermostat("annealing", t_hi=5.0, t_lo=0.0, cycle_len=300)
-    eng = native.Engine(tmpl, [active], terms, aptamer=apt, thermostat=th, device=local_rank, fold_mode=fold)
-    W = a.walkers
-    seqs = workloads.walker_sequences(tmpl, [active], W, seed_base=1000 + gids_rank[0])
-    eng.walkers_init(gids_rank, seqs)
+def roofline_record(eng, events, dc, seqs, fin_seqs, tmpl, active, fold, bppm, length, steps, traced,
+                    traffic_json):
+    """--full: roofline of the dominant kernel of the timed run (`events`, read
+    right after it) and, with `traced`, the executed share of the inside
+    refolds from one traced step after the timed region."""
+    from addapt_amd import roofline
 
-    def barrier():
-        if dist is not None:
-            import torch
-
-            dist.barrier()
-            torch.cuda.synchronize()
-
-    if warmup > 0:
-        eng.run_steps(warmup)
-    _, _, c0 = eng.download()
-    barrier()
-    t0 = time.perf_counter()
-    rx = None
-    audit = None
-    if replica_mode:
-        observe = None
-        if a.replica_audit:
-            audit = {"round": [], "partner": [], "before": [], "after": [], "moved": []}
-
-            def observe(rnd, p, s0, c0, s1, c1):
-                audit["round"].append(rnd)
-                audit["partner"].append(-1 if p is None else p)
-                d0, d1 = replica.digests(s0, c0), replica.digests(s1, c1)
-                audit["before"].append(d0)
-                audit["after"].append(d1)
-                audit["moved"].append(int((d0 != d1).sum()))
-        rx = replica.run(eng, dist, rank, world, steps, a.replica_interval, temps, seed=0, device="cuda",
-                         observe=observe)
-    else:
-        eng.run_steps(steps)
-    barrier()
-    t1 = time.perf_counter()
-    kernel_ms = eng.last_kernel_ms()            # whole timed run_steps (3 kernels per step)
-    score_ms, launches = eng.last_score_kernel_ms()   # the step's score window, per launch
-    inside_ms, outside_ms = eng.last_kernel_split_ms()   # the same window split per kernel
-    inside_name, outside_name = eng.last_kernel_names()  # what the engine launched
-    fin_seqs, fin_scores, c1 = eng.download()
-    elapsed = shard.max_over_ranks(t1 - t0, dist, device=dev)
-    per_rank_ms = shard.gather_over_ranks((t1 - t0) / max(1, steps) * 1e3, dist, device=dev)
-    if dump:
-        import numpy as np
-
-        os.makedirs(dump, exist_ok=True)
-        np.savez(os.path.join(dump, "rank%d.npz" % rank), gids=np.array(gids_rank), seqs=np.array(fin_seqs),
-                 scores=fin_scores, counters=c1, template=np.array([tmpl]), active=np.array([active]),
-                 fold=np.array([fold]), bppm=np.array([bppm]), length=np.array([length]),
-                 kernels=np.array([eng.last_kernel_names()[0], eng.last_kernel_names()[1]]))
+    kernel_ms, (score_ms, launches), (inside_ms, outside_ms), (inside_name, outside_name) = events
     # executed (incremental) vs algorithmic inside work, from one traced step
     # after the timed region (rank 0 reports it)
     ex_inside, full_inside, ex_n = executed_inside_work(eng, fin_seqs, tmpl, active, fold) \
-        if rank == 0 and not replica_mode else (None, None, 0)
-    if audit is not None:
-        import numpy as np
-
-        os.makedirs(a.replica_audit, exist_ok=True)
-        pick = sorted(set(range(0, W, max(1, W // 8))) | {W - 1})
-        np.savez(os.path.join(a.replica_audit, "rank%d.npz" % rank),
-                 round=np.array(audit["round"]), partner=np.array(audit["partner"]),
-                 before=np.array(audit["before"], dtype=np.uint64),
-                 after=np.array(audit["after"], dtype=np.uint64), moved=np.array(audit["moved"]),
-                 temperature=np.array([temps[rank]]), accepted=np.array([rx["accepted"]]),
-                 attempted=np.array([rx["attempted"]]), sample_slots=np.array(pick),
-                 sample_seqs=np.array([fin_seqs[w] for w in pick]),
-                 sample_scores=fin_scores[pick], counters=c1 - c0, template=np.array([tmpl]),
-                 active=np.array([active]), fold=np.array([fold]))
-    value = W * steps * world / elapsed
-
+        if traced else (None, None, 0)
     # algorithmic work of the launch: scored steps x the folds' (+ outside passes') terms
-    dc = c1 - c0
     scored = int(dc[:, 0].sum() + dc[:, 1].sum() + dc[:, 3].sum())
-    outcomes = shard.sum_over_ranks(dc.sum(axis=0), dist, device=dev)
     sample = [tmpl] + seqs[:7]
     work = roofline.pf_flops if fold == "pf" else roofline.mfe_ops
     f_free = sum(work(x, None) for x in sample) / len(sample)
@@ -458,6 +405,125 @@ def measure(a, fold, bppm, length, steps, warmup, rank, world, gids_rank, dist, 
     }
     if traffic and roof["priced_kernel_algorithmic_bytes_per_launch"]:
         roof["traffic_over_algorithmic"] = traffic / roof["priced_kernel_algorithmic_bytes_per_launch"]
+    return roof
+
+
+DUMP_BYTES = 64 << 20
+
+
+def write_outputs(out_dir, rank, world, gids, seqs, scores, counters):
+    """--dump-outputs: what a caller of the timed path holds after its last step
+    (Engine.download), as <name>.npy (<name>_rank<r>.npy with N > 1 ranks):
+    `sequences` (float32 character codes, walkers x length), `scores` and
+    `counters` (float64; the counters include the warm-up steps) and
+    `walker_ids`, the global id of each row.  At most DUMP_BYTES over all
+    ranks: beyond that, a fixed seeded sample of the walkers."""
+    import numpy as np
+
+    W = len(seqs)
+    n = len(seqs[0]) if W else 0
+    per_walker = 4 * n + 8 * (1 + counters.shape[1] + 1)
+    keep = max(1, DUMP_BYTES // max(1, world) // per_walker)
+    rows = np.arange(W)
+    if W > keep:
+        rows = np.sort(np.random.default_rng(0).choice(W, size=keep, replace=False))
+    codes = np.frombuffer("".join(seqs).encode("ascii"), dtype=np.uint8).reshape(W, n)
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = "" if world == 1 else "_rank%d" % rank
+    for name, arr in (("sequences", codes[rows].astype(np.float32)),
+                      ("scores", np.asarray(scores, dtype=np.float64)[rows]),
+                      ("counters", np.asarray(counters)[rows].astype(np.float64)),
+                      ("walker_ids", np.asarray(gids, dtype=np.float64)[rows])):
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), arr)
+
+
+def measure(a, fold, bppm, length, steps, warmup, rank, world, gids_rank, dist, dev, local_rank,
+            traffic_json=None, cpu=False, cpu_seconds=15.0, dump=None, full=False, dump_outputs=None):
+    """Run one workload (W walkers of this rank) and return its record: value
+    (all ranks), ms_per_step, outcomes and, with `full`, the roofline of the
+    dominant kernel."""
+    from addapt_amd import native, shard, workloads
+
+    tmpl, active = workloads.synthetic(length)
+    terms = workloads.config_objective(length, bppm=bppm)
+    apt = (workloads.THEO_SEQ, workloads.THEO_FOLD, native.theo_energy())
+    replica_mode = a.replica_interval > 0 and world > 1
+    if replica_mode:
+        from addapt_amd import replica
+
+        temps = replica.ladder_temperatures(world)
+        th = native.make_thermostat("fixed", t=temps[rank])
+    else:
+        th = native.make_thermostat("annealing", t_hi=5.0, t_lo=0.0, cycle_len=300)
+    eng = native.Engine(tmpl, [active], terms, aptamer=apt, thermostat=th, device=local_rank, fold_mode=fold)
+    W = a.walkers
+    seqs = workloads.walker_sequences(tmpl, [active], W, seed_base=1000 + gids_rank[0])
+    eng.walkers_init(gids_rank, seqs)
+
+    def barrier():
+        if dist is not None:
+            import torch
+
+            dist.barrier()
+            torch.cuda.synchronize()
+
+    if warmup > 0:
+        eng.run_steps(warmup)
+    _, _, c0 = eng.download()
+    barrier()
+    t0 = time.perf_counter()
+    rx = None
+    audit = None
+    if replica_mode:
+        observe = None
+        if a.replica_audit:
+            audit = {"round": [], "partner": [], "before": [], "after": [], "moved": []}
+
+            def observe(rnd, p, s0, c0, s1, c1):
+                audit["round"].append(rnd)
+                audit["partner"].append(-1 if p is None else p)
+                d0, d1 = replica.digests(s0, c0), replica.digests(s1, c1)
+                audit["before"].append(d0)
+                audit["after"].append(d1)
+                audit["moved"].append(int((d0 != d1).sum()))
+        rx = replica.run(eng, dist, rank, world, steps, a.replica_interval, temps, seed=0, device="cuda",
+                         observe=observe)
+    else:
+        eng.run_steps(steps)
+    barrier()
+    t1 = time.perf_counter()
+    events = kernel_events(eng) if full else None
+    fin_seqs, fin_scores, c1 = eng.download()
+    elapsed = shard.max_over_ranks(t1 - t0, dist, device=dev)
+    per_rank_ms = shard.gather_over_ranks((t1 - t0) / max(1, steps) * 1e3, dist, device=dev)
+    if dump:
+        import numpy as np
+
+        os.makedirs(dump, exist_ok=True)
+        np.savez(os.path.join(dump, "rank%d.npz" % rank), gids=np.array(gids_rank), seqs=np.array(fin_seqs),
+                 scores=fin_scores, counters=c1, template=np.array([tmpl]), active=np.array([active]),
+                 fold=np.array([fold]), bppm=np.array([bppm]), length=np.array([length]),
+                 kernels=np.array([eng.last_kernel_names()[0], eng.last_kernel_names()[1]]))
+    if dump_outputs:
+        write_outputs(dump_outputs, rank, world, gids_rank, fin_seqs, fin_scores, c1)
+    if audit is not None:
+        import numpy as np
+
+        os.makedirs(a.replica_audit, exist_ok=True)
+        pick = sorted(set(range(0, W, max(1, W // 8))) | {W - 1})
+        np.savez(os.path.join(a.replica_audit, "rank%d.npz" % rank),
+                 round=np.array(audit["round"]), partner=np.array(audit["partner"]),
+                 before=np.array(audit["before"], dtype=np.uint64),
+                 after=np.array(audit["after"], dtype=np.uint64), moved=np.array(audit["moved"]),
+                 temperature=np.array([temps[rank]]), accepted=np.array([rx["accepted"]]),
+                 attempted=np.array([rx["attempted"]]), sample_slots=np.array(pick),
+                 sample_seqs=np.array([fin_seqs[w] for w in pick]),
+                 sample_scores=fin_scores[pick], counters=c1 - c0, template=np.array([tmpl]),
+                 active=np.array([active]), fold=np.array([fold]))
+    value = W * steps * world / elapsed
+
+    dc = c1 - c0
+    outcomes = shard.sum_over_ranks(dc.sum(axis=0), dist, device=dev)
     rec = {
         "value": value,
         "unit": "MC steps/s",
@@ -481,8 +547,10 @@ def measure(a, fold, bppm, length, steps, warmup, rank, world, gids_rank, dist, 
         "bppm": bppm,
         "length": length,
         "outcomes": {k: int(v) for k, v in zip(native.OUTCOMES, outcomes)},
-        "roofline": roof,
     }
+    if full:
+        rec["roofline"] = roofline_record(eng, events, dc, seqs, fin_seqs, tmpl, active, fold, bppm, length,
+                                          steps, rank == 0 and not replica_mode, traffic_json)
     if rx is not None:
         att = shard.sum_over_ranks([rx["attempted"], rx["accepted"], rx["rounds"]], dist, device=dev)
         rec["exchange"] = {"rounds_per_rank": rx["rounds"], "attempted": att[0], "accepted": att[1],
@@ -555,8 +623,8 @@ def main():
     W = a.walkers
     gids = shard.walker_ids(rank, world, W)
     rec = measure(a, a.fold, a.bppm, a.length, a.steps, a.warmup, rank, world, gids, dist, dev, device,
-                  traffic_json=a.traffic_json, cpu=not a.no_cpu_baseline, cpu_seconds=a.cpu_seconds,
-                  dump=a.dump_walkers)
+                  traffic_json=a.traffic_json, cpu=a.full and not a.no_cpu_baseline, cpu_seconds=a.cpu_seconds,
+                  dump=a.dump_walkers, full=a.full, dump_outputs=a.dump_outputs)
     out = {
         "metric": METRIC,
         "value": rec["value"],
@@ -587,11 +655,12 @@ def main():
             "shared_device": bool(a.share_device and world > 1),
             "outcomes": rec["outcomes"],
         },
-        "roofline": rec["roofline"],
         # the collective backend torch.distributed ran ("nccl" = RCCL on ROCm), the
         # world size it reported, each rank's ms per step and their max (the value's clock)
         "dist": rec["dist"],
     }
+    if "roofline" in rec:
+        out["roofline"] = rec["roofline"]
     if "exchange" in rec:
         out["exchange"] = rec["exchange"]
     if "cpu_baseline" in rec:
@@ -599,14 +668,14 @@ def main():
     # the reference's own scoring path (vrna_pf, scoring.cc:53-71) measured in the
     # same run: PF, config 3 (pf + bppm, N = 100) and config 4's per-GPU shard
     # (pf + bppm, N = 150), each with its dominant kernel's roofline
-    if not a.no_sub_records and a.fold == "mfe" and not a.bppm and a.replica_interval == 0:
+    if a.full and not a.no_sub_records and a.fold == "mfe" and not a.bppm and a.replica_interval == 0:
         subs = {}
         for name, fold, bppm, length, steps, cpu in (
                 ("pf", "pf", False, 100, a.steps, True),
                 ("config3", "pf", True, 100, a.steps, True),
                 ("config4", "pf", True, 150, min(a.steps, a.sub_steps_c4), False)):
             r = measure(a, fold, bppm, length, steps, min(a.warmup, 5), rank, world, gids, dist, dev, device,
-                        cpu=cpu and not a.no_cpu_baseline, cpu_seconds=a.cpu_seconds * 2.0 / 3.0)
+                        cpu=cpu and not a.no_cpu_baseline, cpu_seconds=a.cpu_seconds * 2.0 / 3.0, full=True)
             subs[name] = {k: r[k] for k in ("value", "unit", "steps", "ms_per_step", "dtype", "workload",
                                             "outcomes", "roofline") if k in r}
             if "cpu_baseline" in r:

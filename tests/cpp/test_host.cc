@@ -300,7 +300,8 @@ static void test_yaml_and_config() {
     CHECK(!n["missing"]);
     CHECK_THROWS(yaml::parse("a: 1\n  b: 2\n"));
     CHECK_THROWS(yaml::parse("a: 1\na: 2\n"));
-    const string path = "/tmp/adx_test_cfg.yml", path2 = "/tmp/adx_test_cfg2.yml";
+    // scratch files go to the working directory (the test runs this in its own tmp dir)
+    const string path = "adx_test_cfg.yml", path2 = "adx_test_cfg2.yml";
     { std::ofstream f(path); f << cfg; }
     auto dev = device_from_yaml({path});
     CHECK(dev->seq() == "ACGUacguNNNN" && dev->macrostate("active") == "((..))......");
@@ -330,7 +331,7 @@ static void test_reference_loop_and_tsv() {
     mc += std::make_shared<UnbiasedMutationMove>();
     mc.scorefxn(sf);
     mc.num_steps(20);
-    const string path = "/tmp/adx_test_traj.tsv";
+    const string path = "adx_test_traj.tsv";
     mc += std::make_shared<TsvTrajectoryReporter>(path, 2);
     std::mt19937 rng(0);
     DevicePtr out = mc.apply(dev, rng);

@@ -30,7 +30,7 @@ def _bench(extra, timeout=240):
 
 @pytest.mark.gpu
 def test_bench_two_ranks_sharded():
-    out = _bench([])
+    out = _bench(["--full"])   # the roofline is part of a --full line
     assert out["n_gpus"] == 2 and out["config"]["global_walkers"] == 2 * W
     assert out["config"]["dist_backend"] == "gloo" and out["config"]["shared_device"]
     assert sum(out["config"]["outcomes"].values()) == 2 * W * STEPS   # summed over ranks

@@ -25,7 +25,8 @@ def test_cpp_host_unit_tests(host_lib, tmp_path):
     subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-I", os.path.join(ROOT, "include"), "-o", exe,
                     os.path.join(ROOT, "tests", "cpp", "test_host.cc"), "-L", host_lib, "-laddapt_host",
                     "-laddapt_gpu", "-Wl,-rpath," + host_lib], check=True)
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=120)
+    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=120,
+                       cwd=str(tmp_path))   # its scratch files land there
     assert r.returncode == 0, r.stdout
     assert " 0 failed" in r.stdout
 

@@ -6,7 +6,8 @@
 #   pytest:<name>:<pytest args>     e.g. 'pytest:mfe:tests/test_gpu_mfe.py -k auto'
 #   suite                           the whole -m gpu suite (pytest_gpu.txt)
 #   smoke                           __graft_entry__.smoke()
-#   bench:<name>:<bench.py args>    one bench line -> <name>.json
+#   bench:<name>:<bench.py args>    one bench line -> <name>.json (args '--full ...': with the
+#                                   roofline, the CPU baseline and the sub-records)
 #   prof:<name>:<bench.py args>     rocprofv3 --kernel-trace --stats of a bench run
 #   pmc:<name>:<bench.py args>      three PMC passes (SQ occupancy / instruction
 #                                   mix / LDS), kernel trace only, per dispatch

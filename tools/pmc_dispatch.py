@@ -15,7 +15,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--kernel", required=True)
     ap.add_argument("--ops-per-launch", type=float, default=None,
-                    help="algorithmic lane-ops per MC launch (bench.py roofline flop_per_launch)")
+                    help="algorithmic lane-ops per MC launch (bench.py --full, roofline flop_per_launch)")
     ap.add_argument("--lane-ops-per-inst", type=float, default=64.0,
                     help="useful ops one VALU instruction can do (64 lanes; x2 for packed 16-bit)")
     ap.add_argument("csv", nargs="+")

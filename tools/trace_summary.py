@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-step duration of the score kernel(s) in a rocprofv3 kernel trace
-(bench_kernel_trace.csv), comparable with bench.py's
+(bench_kernel_trace.csv), comparable with `bench.py --full`'s
 roofline.kernel_ms_per_launch (HIP events around each step's score launch,
 which for the MFE fold covers the packed 16-bit kernel and its FP32 fallback
 launch).  For every score_kernel instantiation the LAST `--last K` launches
