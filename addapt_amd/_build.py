@@ -17,8 +17,10 @@ OBJ = os.path.join(OUT, "obj")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
-GPU_SOURCES = ["kernels.hip", "mfe_cells.hip", "mfe_pair.hip", "outside_cells.hip", "pf_cells.hip", "pf_ring.hip", "outside_ring.hip", "adx_api.cpp",
-               "energy.cpp"]
+# the one list of the engine's sources (tools/build_variant.py builds from it too)
+GPU_SOURCES = ["fold_rows.hip", "mc_step.hip", "dispatch.hip", "mfe_cells.hip", "mfe_pair.hip", "outside_cells.hip",
+               "pf_cells.hip", "pf_ring.hip", "outside_ring.hip", "adx_api.cpp", "energy.cpp"]
+GPU_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 
 
 def _newer(src_list, out):
@@ -35,21 +37,26 @@ def _run(cmd):
     return r.stdout
 
 
-def build_gpu(force=False):
-    os.makedirs(OBJ, exist_ok=True)
-    lib = os.path.join(OUT, "libaddapt_gpu.so")
+def build_gpu(force=False, out_dir=None, lib_name="libaddapt_gpu.so", extra_flags=(), replace=None):
+    """The engine library.  A variant build (tools/build_variant.py) names its
+    own out_dir / lib_name, adds extra_flags to every compile, and maps source
+    names to replacement paths (replace); headers still come from csrc/."""
+    out = out_dir or OUT
+    obj = os.path.join(out, "obj")
+    os.makedirs(obj, exist_ok=True)
+    lib = os.path.join(out, lib_name)
     # generated shape blocks (*.inc) are included by the kernels: a change must rebuild them
     headers = (glob.glob(os.path.join(CSRC, "*.hpp")) + glob.glob(os.path.join(CSRC, "*.inc")) +
                [os.path.join(ROOT, "include", "addapt_gpu.h")])
     jobs = []
     objs = []
     for src in GPU_SOURCES:
-        s = os.path.join(CSRC, src)
-        o = os.path.join(OBJ, src + ".o")
+        s = (replace or {}).get(src, os.path.join(CSRC, src))
+        o = os.path.join(obj, src + ".o")
         objs.append(o)
         if force or _newer([s] + headers, o):
-            jobs.append([HIPCC, "--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall",
-                         "-Wno-unused-function", "-c", s, "-o", o])
+            inc = ["-I", CSRC] if s != os.path.join(CSRC, src) else []   # a replacement includes csrc's headers
+            jobs.append([HIPCC, "--offload-arch=" + ARCH] + GPU_FLAGS + list(extra_flags) + inc + ["-c", s, "-o", o])
     with ThreadPoolExecutor(max_workers=4) as ex:
         list(ex.map(_run, jobs))
     if force or jobs or not os.path.exists(lib):

@@ -1,6 +1,6 @@
 // C ABI of the MI355X engine (include/addapt_gpu.h): run setup on the host,
 // device buffers, kernel launches.  The reference's objects this replaces are
-// cited per function; the heavy lifting is in kernels.hip.
+// cited per function; the heavy lifting is in the .hip files (launch.hpp).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -19,25 +19,7 @@
 #include "../../include/addapt_gpu.h"
 #include "dev_types.hpp"
 #include "energy.hpp"
-
-namespace adx {
-size_t lds_bytes(const KArgs &ka, bool qbm, int nt);
-hipError_t launch_score(const KArgs &ka, bool qbm, const uint8_t *seqs, int W, double *scores,
-                        double *terms, float *dG, hipStream_t stream);
-hipError_t launch_steps(const KArgs &ka, bool qbm, const StepArgs &st, hipStream_t stream, hipEvent_t *evs);
-hipError_t launch_rescore(const KArgs &ka, const StepArgs &st, double *tv, hipStream_t stream);
-const char *inside_kernel_name(const KArgs &ka);
-size_t pf_ring_lds(const KArgs &ka);
-size_t outside_ring_lds(const KArgs &ka);
-size_t pf_ring_scratch_floats(const KArgs &ka, int W);
-const char *outside_kernel_name(const KArgs &ka);
-size_t bppm_lds_bytes(const KArgs &ka, bool *gout);
-size_t bppm_scratch_bytes(const KArgs &ka, int W);
-hipError_t launch_bppm(const KArgs &ka, const uint8_t *seqs, int W, const int *mask, double *full, int ld,
-                       double *pair_p, char *scratch, hipStream_t stream);
-constexpr int NT = 512;
-constexpr size_t LDS_MAX = 163840;
-}  // namespace adx
+#include "launch.hpp"
 
 using namespace adx;
 
@@ -328,7 +310,7 @@ void build_scaled(const EnergyParams &P, double sigma, const Motif &m, double ei
 }
 
 // Dot-bracket hard constraint (DB_DEFAULT | ENFORCE_BP, scoring.cc:61-62) ->
-// five byte arrays of length N+2: up, dn, ptn, enc, flg (see kernels.hip).
+// five byte arrays of length N+2: up, dn, ptn, enc, flg (see fold_common.hpp allowed()).
 adx_status build_constraint(const std::string &cst, int N, std::vector<uint8_t> &out) {
     const int np = N + 2;
     out.assign(5 * np, 0);
@@ -408,13 +390,12 @@ struct Problem {
     double g0 = -0.30;  // assumed free energy per nucleotide for the pf scale
     std::vector<DevVariant> variants;
     std::vector<int> vmac;       // per variant: macrostate index, -1 = unconstrained
-    std::vector<int> groups2;    // variant pairs folded in lockstep (kernels.hip pf_group)
+    std::vector<int> groups2;    // variant pairs folded in lockstep (fold_rows.hip pf_group)
     std::vector<uint8_t> cons;
     std::vector<uint8_t> ctx_seq;
     std::vector<int> ctx_off;
     std::vector<DevTermMap> tmap;
     int n_terms = 0, n_ctx_eff = 1;
-    bool qbm = true;
     int mode = 0;                // 0 = partition functions, 1 = MFE (ADX_FOLD_*)
     DevBuf<DevTables> dT;
     DevBuf<DevScaled> dX;
@@ -429,15 +410,15 @@ struct Problem {
     DevBuf<int> dBvars, dPairs, dBvarSlot;
     DevBuf<double> dPairP;
     DevBuf<char> dScratch;       // outside tables in HBM when they do not fit LDS
-    bool pf_ring = false;        // PF folds by pf_ring_kernel (fixes the slot layout, kernels.hip)
+    bool pf_ring = false;        // PF folds by pf_ring_kernel (fixes the slot layout, dispatch.hip pf_ring_layout)
     DevBuf<float> dRingScr;      // its qb scratch for stateless launches
-    // MFE: packed 16-bit copies of the energy tables (kernels.hip MinPlus16)
+    // MFE: packed 16-bit copies of the energy tables (fold_rows.hip MinPlus16)
     DevBuf<DevTables> dT16;
     DevBuf<DevScaled> dX16;
     DevBuf<int> dOvf;
     bool mfe16 = false;
     bool mfe_cells_ok = false;   // Ninio saturated from |n1-n2| = 5 on, MLbase >= 0 (mfe_cells.hip)
-    // incremental-fold state of the MC walkers (kernels.hip Inc)
+    // incremental-fold state of the MC walkers (fold_rows.hip Inc)
     DevBuf<float> dTab;
     DevBuf<float> dGstep;        // [W][n_variants] energies of the step's folds (pf_cells_kernel,
                                  //   and the pair-term score that waits for the outside pass)
@@ -514,17 +495,12 @@ struct Problem {
         return ka;
     }
 
-    adx_status choose_layout() {
-        KArgs ka = kargs();
-        const char *env = std::getenv("ADX_QBM");
-        const size_t with = lds_bytes(ka, true, NT), without = lds_bytes(ka, false, NT);
-        if (env) qbm = std::atoi(env) != 0;
-        else if (with * 2 <= LDS_MAX) qbm = true;
-        else if (without * 2 <= LDS_MAX) qbm = false;
-        else qbm = with <= LDS_MAX;
-        if (lds_bytes(ka, qbm, NT) > LDS_MAX)
-            return fail(ADX_EUNSUPPORTED, "sequence length %d needs %zu B of LDS (> %zu)", Nmax,
-                        lds_bytes(ka, qbm, NT), LDS_MAX);
+    // every context must fit the rows kernel (the fallback of every other fold kernel)
+    adx_status check_lds() {
+        const size_t need = lds_bytes(kargs());
+        if (need > size_t(LDS_LIMIT))
+            return fail(ADX_EUNSUPPORTED, "sequence length %d needs %zu B of LDS (> %zu)", Nmax, need,
+                        size_t(LDS_LIMIT));
         return ADX_OK;
     }
 
@@ -652,21 +628,14 @@ struct Problem {
         HIP_TRY(dBvarSlot.upload(bslot.data(), bslot.size(), stream));
         HIP_TRY(dPairs.upload(pairs.data(), pairs.size(), stream));
         HIP_TRY(hipStreamSynchronize(stream));
-        // PF folds longer than pf_cells covers take the ring kernel (pf_ring.hip).
-        // One choice per context: it fixes the layout of the walkers' stored
-        // tables, which every later kernel of the context must read the same way.
-        {
-            pf_ring = false;
-            const char *e = std::getenv("ADX_PF_KERNEL");
-            const bool rows = e && std::strcmp(e, "rows") == 0;
-            const KArgs k = kargs();
-            pf_ring = mode == 0 && !rows && pf_ring_lds(k) > 0 && (pairs.empty() || outside_ring_lds(k) > 0);
-        }
+        // the slot layout of the walkers' stored tables: one choice per context
+        pf_ring = false;
+        pf_ring = pf_ring_layout(kargs());
         s = upload_mfe16();
         if (s) return s;
         if (!pairs.empty() && bppm_lds_bytes(kargs(), nullptr) == 0)
             return fail(ADX_EUNSUPPORTED, "base-pair probabilities of length %d do not fit one CU's LDS yet", Nmax);
-        return choose_layout();
+        return check_lds();
     }
 
     // per-walker pair-probability buffer (grow-only)
@@ -706,7 +675,7 @@ struct Problem {
         if (so) return so;
         if (!pairs.empty())
             HIP_TRY(launch_bppm(kargs(), dseqs, W, nullptr, nullptr, 0, dPairP.p, dScratch.p, stream));
-        HIP_TRY(launch_score(kargs(), qbm, dseqs, W, dscores, dterms, ddG, stream));
+        HIP_TRY(launch_score(kargs(), dseqs, W, dscores, dterms, ddG, stream));
         return ADX_OK;
     }
 };
@@ -1193,7 +1162,7 @@ static void mt_seed_host(uint32_t seed, uint32_t *mt) {
 }
 
 // Every walker's current configuration folded from scratch by the MC step's
-// kernels (kernels.hip launch_rescore): fresh scores to prop_score, term
+// kernels (mc_step.hip launch_rescore): fresh scores to prop_score, term
 // values to dtv (device, optional), fresh tables adopted.
 static adx_status rescore_walkers(adx_ctx *c, double *dtv) {
     Problem &pb = c->pb;
@@ -1358,7 +1327,7 @@ extern "C" adx_status adx_run_steps(adx_ctx *c, int steps, adx_trace *trace) {
     pb.state_on = false;
     c->inside_kernel = inside_kernel_name(ka_steps);
     c->outside_kernel = outside_kernel_name(ka_steps);
-    HIP_TRY(launch_steps(ka_steps, pb.qbm, st, pb.stream, evs.data()));
+    HIP_TRY(launch_steps(ka_steps, st, pb.stream, evs.data()));
     HIP_TRY(hipEventRecord(c->ev1, pb.stream));
     HIP_TRY(hipEventSynchronize(c->ev1));
     float ms = 0.f;
@@ -1370,7 +1339,7 @@ extern "C" adx_status adx_run_steps(adx_ctx *c, int steps, adx_trace *trace) {
         HIP_TRY(hipEventElapsedTime(&e, evs[4 * k], evs[4 * k + 3]));
         HIP_TRY(hipEventElapsedTime(&b, evs[4 * k + 1], evs[4 * k + 2]));
         sk += e;
-        si += e - b;   // the window minus its outside pass (kernels.hip launch_steps)
+        si += e - b;   // the window minus its outside pass (mc_step.hip launch_steps)
         so += b;
     }
     c->score_ms_total = sk;

@@ -1,0 +1,48 @@
+// The score combination shared by the MC step tail (mc_step.hip) and
+// combine_kernel (dispatch.hip): one term's value, and a walker's score by one wave.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include "dev_types.hpp"
+#include "fold_common.hpp"
+
+namespace adx {
+namespace {
+
+// combine_score's arithmetic (scoring.cc:53-71): term idx (= context * n_terms
+// + term) of the walker whose per-variant energies are g and pair
+// probabilities pp (null: the pair terms read 0.5)
+__device__ __forceinline__ double term_value(const KArgs &ka, const float *g, const double *pp, int idx,
+                                             double &weight) {
+    const DevTermMap m = ka.tmap[idx];
+    double p = (m.kind == 1) ? (pp ? pp[m.pidx] : 0.5)
+                             : exp((static_cast<double>(g[m.vfree]) - static_cast<double>(g[m.vcons])) / ka.X->kT);
+    if (!m.favorable) p = 1.0 - p;
+    weight = m.weight;
+    return log(p);
+}
+
+// The score of walker w from KArgs::gstep, one wave: the terms' values on
+// lanes, summed in term order (the same sum as combine_kernel's loop); tv
+// (the walker's term values, optional).  Result uniform.
+__device__ double combine_wave(const KArgs &ka, int w, int lane, double *tv) {
+    const float *g = ka.gstep + size_t(w) * ka.n_variants;
+    const double *pp = ka.pair_p ? ka.pair_p + size_t(w) * ka.n_pairs : nullptr;
+    const int nt = ka.n_terms * ka.n_ctx_eff;
+    double score = 0.0;
+    for (int b0 = 0; b0 < nt; b0 += WAVE) {
+        const int idx = b0 + lane;
+        double val = 0.0, wt = 0.0;
+        if (idx < nt) {
+            val = term_value(ka, g, pp, idx, wt);
+            if (tv) tv[idx] = val;
+        }
+        const int n = min(WAVE, nt - b0);
+        for (int k = 0; k < n; k++) score += __shfl(wt, k, WAVE) * __shfl(val, k, WAVE);
+    }
+    return score;
+}
+
+}  // namespace
+}  // namespace adx

@@ -55,7 +55,7 @@ enum TermKind : uint8_t { TK_STK = 0, TK_B1, TK_I11, TK_I12, TK_I21, TK_I22, TK_
 // FP32 Boltzmann factors (with the pf scale sigma^k), "impossible" = 0.
 // Minimum free energy (mode 1): the same layouts hold energies in dcal/mol
 // (integers, exact in FP32), factor products become sums, sigma^k becomes 0,
-// "impossible" = MFE_BIG (kernels.hip MinPlus).
+// "impossible" = MFE_BIG (fold_rows.hip MinPlus).
 constexpr float MFE_BIG = 1.0e7f;
 constexpr float MFE_MARK = 3.0e7f;   // non-pairable cell mark of the MFE tables
 
@@ -142,7 +142,7 @@ __host__ __device__ inline size_t inc_cc_floats(int cells) { return (size_t(cell
 __host__ __device__ inline size_t inc_cc_offset(int cells, int Nmax, int n_groups2, int g) {
     return (size_t(n_groups2) * inc_group_floats(cells, Nmax, 1) + 3) / 4 * 4 + size_t(g) * inc_cc_floats(cells);
 }
-// the same for the PF slots (two value arrays per group: pf_cells.hip, kernels.hip SumProd)
+// the same for the PF slots (two value arrays per group: pf_cells.hip, fold_rows.hip SumProd)
 __host__ __device__ inline size_t inc_cc_offset_pf(int cells, int Nmax, int n_groups2, int g) {
     return (size_t(n_groups2) * inc_group_floats(cells, Nmax, 2) + 3) / 4 * 4 + size_t(g) * inc_cc_floats(cells);
 }
@@ -163,7 +163,7 @@ struct KArgs {
     int cells;                  // (Nmax-4)(Nmax-3)/2
     const int *groups2;         // [n_groups2][2]: variants folded in lockstep (apo, holo of one
     int n_groups2;              //   (context, macrostate); a lone variant is paired with itself)
-    int opt;                    // launch-time LDS options (kernels.hip choose_opt)
+    int opt;                    // launch-time LDS options (fold_rows.hip choose_opt)
     int mode;                   // 0 = partition functions, 1 = minimum free energies (MinPlus tables)
     // base-pair probabilities (outside pass, bppm_kernel)
     const int *bvars;           // [n_bvars] variants folded with an outside pass
@@ -180,7 +180,7 @@ struct KArgs {
     const DevScaled *X16;
     int *ovf;
     int mfe_cells_ok;           // the lanes = cells MFE kernel covers this energy model (mfe_cells.hip)
-    // incremental folds (kernels.hip Inc): per walker two slots of every group's
+    // incremental folds (fold_rows.hip Inc): per walker two slots of every group's
     // tables (tab_slot floats each), the current slot and whether it is valid,
     // and the hull of the positions the step's proposal changed (-1: none)
     float *tab;
@@ -199,13 +199,13 @@ struct KArgs {
     // (re-using the inside tables just written) -> combine_kernel
     float *gstep;
     // MC steps: the walkers in launch order, heaviest refold first, so the long
-    // folds do not trail the launch (kernels.hip order_kernel, from the weight
+    // folds do not trail the launch (mc_step.hip order_kernel, from the weight
     // classes in ocls); the fold kernels map blockIdx through it
     // (fold_common.hpp walker_at); null: blockIdx order
     int *order;
     const uint8_t *ocls;
     // MC steps: the scores a fold launch leaves as per-variant energies in gstep
-    // are combined by the step's tail (kernels.hip accept_walker), not by a
+    // are combined by the step's tail (mc_step.hip accept_walker), not by a
     // combine_kernel launch of their own
     int defer_comb;
 };

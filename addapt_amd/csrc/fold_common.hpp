@@ -1,4 +1,4 @@
-// Helpers shared by the fold kernels (kernels.hip, mfe_cells.hip): cell
+// Helpers shared by the fold kernels (fold_rows.hip, mfe_cells.hip, ...): cell
 // indexing of the DP tables, pair types, the LDS-only barrier, the packed
 // 16-bit min-plus encoding and the per-cell table block layout.
 #pragma once
@@ -6,6 +6,25 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+
+#include "dev_types.hpp"
+
+// Diagnostic builds (-DADX_STAMP) only, never the product: add the cycles
+// (s_memtime) since the wave's last stamp to its phase counter k.  st_acc and
+// st_last are the kernel's locals; each kernel copies st_acc to its own
+// g_stamps_* array, read back through its adx_debug_stamps*() export.
+#ifdef ADX_STAMP
+#define ADX_STAMP_AT(k) do { __builtin_amdgcn_sched_barrier(0); const unsigned long long t_ = __builtin_amdgcn_s_memtime(); st_acc[k] += t_ - st_last; st_last = t_; __builtin_amdgcn_sched_barrier(0); } while (0)
+#else
+#define ADX_STAMP_AT(k) do { } while (0)
+#endif
+
+// The four-lanes-per-cell interior-loop sweeps (pf_cells.hip, pf_ring.hip,
+// outside_common.hpp) compute the sizes <= 5 on phase 0 only (the other
+// phases' copies are discarded); 0: on every phase
+#ifndef ADX_SMALL_R0
+#define ADX_SMALL_R0 1
+#endif
 
 namespace adx {
 namespace {
@@ -39,7 +58,7 @@ __device__ __forceinline__ bool block_or(int *w, bool v) {
 }
 
 // The walker a fold workgroup takes at launch position wb (order: a step's
-// launch order, kernels.hip order_kernel; null: blockIdx order), or -1 when
+// launch order, mc_step.hip order_kernel; null: blockIdx order), or -1 when
 // mask (1 = fold) leaves it nothing to fold.
 __device__ __forceinline__ int walker_at(const int *order, const int *mask, int wb) {
     const int w = order ? order[wb] : wb;
@@ -71,7 +90,7 @@ __device__ __forceinline__ WalkerRef walker_ref(const K &ka, const int *mask, in
 
 typedef short s16x2 __attribute__((ext_vector_type(2)));
 constexpr int MFE16_FLOOR = -12000;
-// Exactness of the packed 16-bit MFE encoding (kernels.hip MinPlus16): a half
+// Exactness of the packed 16-bit MFE encoding (fold_rows.hip MinPlus16): a half
 // >= 0x4000 is "impossible".  A true finite value can only reach that band as
 // a sum of at most two stored values plus loop constants (each < 40.96
 // kcal/mol, i.e. < 0x1000), so while every stored finite value is below
@@ -110,6 +129,35 @@ __device__ __forceinline__ int special_hp(const uint32_t *spk, uint32_t key) {
         }
     }
     return hit;
+}
+
+// ---------------------------------------------------------------- hard constraints
+// flg bits: 1 = 'x' (no pair), 2 = '<' (pairs upstream), 4 = '>' (downstream);
+// ptn = enforced partner (0 none); enc = innermost enclosing enforced pair id.
+// L: any LDS carve with the byte arrays flg, ptn, enc.
+template <class LT>
+__device__ __forceinline__ bool allowed(const LT &L, int i, int j) {
+    const int fi = L.flg[i], fj = L.flg[j];
+    if ((fi | fj) & 1) return false;
+    if ((fi & 2) || (fj & 4)) return false;
+    const int pi = L.ptn[i], pj = L.ptn[j];
+    if (pi) return pi == j;
+    if (pj) return pj == i;
+    return L.enc[i] == L.enc[j];
+}
+
+// interior-loop shape kinds (dev_types.hpp TermKind; -1 = generic)
+__host__ __device__ constexpr int loop_kind(int n1, int n2) {
+    return (n1 == 0 && n2 == 0) ? TK_STK
+         : (n1 + n2 == 1) ? TK_B1
+         : (n1 == 0 || n2 == 0) ? TK_BUL
+         : (n1 == 1 && n2 == 1) ? TK_I11
+         : (n1 == 1 && n2 == 2) ? TK_I12
+         : (n1 == 2 && n2 == 1) ? TK_I21
+         : (n1 == 2 && n2 == 2) ? TK_I22
+         : ((n1 == 2 && n2 == 3) || (n1 == 3 && n2 == 2)) ? TK_M23
+         : (n1 == 1 || n2 == 1) ? TK_1N
+         : -1;
 }
 
 // Pair type / reversed type / terminal-AU flag without a memory lookup:

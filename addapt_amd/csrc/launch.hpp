@@ -1,0 +1,99 @@
+// Host interface of the engine's translation units: every function that
+// crosses a file is declared here, once.  Each .hip file and adx_api.cpp
+// include it; none declares another file's function by hand.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+#include <map>
+#include <mutex>
+
+#include "dev_types.hpp"
+
+namespace adx {
+
+// LDS one workgroup may take (gfx950: 160 KiB per CU)
+constexpr int LDS_LIMIT = 160 * 1024;
+
+// Raise `kernel`'s dynamic-LDS limit to `bytes` (grow-only, one record per
+// kernel).  no_static_lds: the kernel carves LDS from address 0, so static LDS
+// in front of the dynamic block is an error.
+template <class K>
+inline hipError_t configure_dynamic_lds(K kernel, size_t bytes, bool no_static_lds = false) {
+    static std::map<const void *, size_t> configured;
+    static std::mutex guard;   // contexts may launch from several host threads
+    const std::lock_guard<std::mutex> lock(guard);
+    const void *k = reinterpret_cast<const void *>(kernel);
+    size_t &have = configured[k];
+    if (bytes <= have) return hipSuccess;
+    if (no_static_lds) {
+        hipFuncAttributes fa;
+        hipError_t e = hipFuncGetAttributes(&fa, k);
+        if (e != hipSuccess) return e;
+        if (fa.sharedSizeBytes != 0) return hipErrorInvalidKernelFile;
+    }
+    hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, int(bytes));
+    if (e == hipSuccess) have = bytes;
+    return e;
+}
+
+// ---- fold_rows.hip: lanes = terms fold (score_kernel) and bppm_kernel
+enum class RowsK { MinPlus16, MinPlusP2, MinPlus512, SumProdP2, SumProd768, SumProd512 };
+const char *rows_kernel_name(RowsK k);
+size_t lds_bytes(const KArgs &ka);
+int rows_lockstep(const KArgs &ka);        // 2: apo and holo fold in lockstep (their LDS fits one CU), else 1
+bool rows_one_per_cu(const KArgs &ka);     // the one-variant tables leave no room for a second workgroup
+hipError_t launch_score_rows(RowsK k, const KArgs &ka, const uint8_t *seqs, int W, double *scores, double *terms,
+                             float *dG, const int *mask, hipStream_t stream, int grid = 0);
+size_t bppm_lds_bytes(const KArgs &ka, bool *gout);
+size_t bppm_scratch_bytes(const KArgs &ka, int W);
+hipError_t launch_bppm_rows(const KArgs &ka, const uint8_t *seqs, int W, const int *mask, double *full, int ld,
+                            double *pair_p, char *scratch, hipStream_t stream, bool reuse);
+
+// ---- mfe_cells.hip, mfe_pair.hip
+size_t mfe_cells_lds(const KArgs &ka);
+hipError_t launch_mfe_cells(const KArgs &ka, const uint8_t *seqs, int W, float *gout, const int *mask,
+                            hipStream_t stream);
+bool mfe_pair_covers(const KArgs &ka);
+hipError_t launch_mfe_pair(const KArgs &ka, const uint8_t *seqs, int W, float *gout, const int *mask,
+                           hipStream_t stream);
+
+// ---- pf_cells.hip, pf_ring.hip
+size_t pf_cells_lds(const KArgs &ka);
+hipError_t launch_pf_cells(const KArgs &ka, const uint8_t *seqs, int W, const int *mask, float *gout,
+                           hipStream_t stream);
+size_t pf_ring_lds(const KArgs &ka);
+size_t pf_ring_scratch_floats(const KArgs &ka, int W);
+hipError_t launch_pf_ring(const KArgs &ka, const uint8_t *seqs, int W, const int *mask, float *gout,
+                          float *qscr, hipStream_t stream);
+
+// ---- outside_cells.hip, outside_ring.hip
+size_t outside_cells_lds(const KArgs &ka);
+hipError_t launch_outside_cells(const KArgs &ka, const uint8_t *seqs, int W, const int *mask, double *pair_p,
+                                int sp_score, hipStream_t stream);
+size_t outside_ring_lds(const KArgs &ka);
+hipError_t launch_outside_ring(const KArgs &ka, const uint8_t *seqs, int W, const int *mask, double *pair_p,
+                               hipStream_t stream);
+
+// ---- dispatch.hip: which kernel folds a workload
+bool pf_ring_layout(const KArgs &ka);      // the context's stored tables take the ring's slot layout
+const char *inside_kernel_name(const KArgs &ka);
+const char *outside_kernel_name(const KArgs &ka);
+bool window_defers(const KArgs &ka);
+hipError_t launch_score_m(const KArgs &ka, const uint8_t *seqs, int W, double *scores, double *terms,
+                          float *dG, const int *mask, hipStream_t stream);
+hipError_t launch_score(const KArgs &ka, const uint8_t *seqs, int W, double *scores, double *terms, float *dG,
+                        hipStream_t stream);
+hipError_t launch_bppm(const KArgs &ka, const uint8_t *seqs, int W, const int *mask, double *full, int ld,
+                       double *pair_p, char *scratch, hipStream_t stream);
+hipError_t launch_outside_m(const KArgs &ka, const uint8_t *seqs, int W, const int *mask, hipStream_t stream);
+hipError_t launch_combine(const KArgs &ka, int W, const int *mask, double *scores, double *terms,
+                          hipStream_t stream);
+
+// ---- mc_step.hip
+hipError_t launch_steps(const KArgs &ka, const StepArgs &st, hipStream_t stream, hipEvent_t *evs);
+hipError_t launch_rescore(const KArgs &ka, const StepArgs &st, double *tv, hipStream_t stream);
+
+}  // namespace adx

@@ -69,17 +69,6 @@ __device__ __forceinline__ T *lds_at(size_t a) {
     return (T *)((__attribute__((address_space(3))) char *)(uint32_t(a)));
 }
 
-template <class LT>
-__device__ __forceinline__ bool allowed(const LT &L, int i, int j) {   // kernels.hip allowed()
-    const int fi = L.flg[i], fj = L.flg[j];
-    if ((fi | fj) & 1) return false;
-    if ((fi & 2) || (fj & 4)) return false;
-    const int pi = L.ptn[i], pj = L.ptn[j];
-    if (pi) return pi == j;
-    if (pj) return pj == i;
-    return L.enc[i] == L.enc[j];
-}
-
 // The per-size energy records (DevScaled::ku16) through the constant address
 // space: uniform loads from it are scalar (s_load, lgkmcnt).  Through a generic
 // pointer they were flat loads, which count on vmcnt too, so the first record

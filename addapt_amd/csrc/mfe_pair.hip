@@ -38,15 +38,14 @@
 
 #include "dev_types.hpp"
 #include "fold_common.hpp"
+#include "launch.hpp"
 #include "mfe_common.hpp"
 
 namespace adx {
 
+#define PSTAMP(k) ADX_STAMP_AT(k)   // fold_common.hpp
 #ifdef ADX_STAMP
 __device__ unsigned long long g_stamps_p[16][16];
-#define PSTAMP(k) do { __builtin_amdgcn_sched_barrier(0); const unsigned long long t_ = __builtin_amdgcn_s_memtime(); st_acc[k] += t_ - st_last; st_last = t_; __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define PSTAMP(k) do { } while (0)
 #endif
 
 namespace {
@@ -942,13 +941,8 @@ __device__ __forceinline__ void mfe_pair_fold(const KArgs &ka, const DevScaled *
                     if (sh >= 1) acc = fold_halves(acc);
                     if (r == 0) {
                         int *pp = L.part + (dd & 3) * 2 * NP + i;
-#ifndef ADX_ABL_NOATOM
                         atomicMin(pp, sext_lo(acc));
                         atomicMin(pp + NP, sext_hi(acc));
-#else   // diagnostic (results wrong): plain stores instead of the atomic minima
-                        pp[0] = sext_lo(acc);
-                        pp[NP] = sext_hi(acc);
-#endif
                     }
                 }
             }
@@ -958,11 +952,7 @@ __device__ __forceinline__ void mfe_pair_fold(const KArgs &ka, const DevScaled *
         // ---------------- M: split parts of qm for spans d and d+1 (lanes = cells x
         // slices of the split points, mfe_cells.hip): min over t >= 5 of
         // qm(i, i+t-1) + qm1(i+t, j), written to the span's slot for F
-#ifndef ADX_ABL_NOM
         if (wid == mw[0] || wid == mw[1]) {
-#else   // diagnostic (results wrong): no split parts
-        if (false) {
-#endif
             __builtin_amdgcn_s_setprio(PRIO_ROLE);
             {
                 const int s = wid == mw[0] ? d : d + 1;
@@ -1252,23 +1242,19 @@ static hipError_t launch_pair_nm(const KArgs &ka, const uint8_t *seqs, int W, fl
                                  hipStream_t stream) {
     constexpr size_t lds = PLay<NM>::BYTES;
     auto k = mfe_pair_kernel<NWV * WAVE, NM>;
-    static bool configured = false;
-    if (!configured) {
-        // the carve addresses LDS from 0 (lds_at): no static LDS may precede the block
+    // the carve addresses LDS from 0 (lds_at): no static LDS may precede the block
+    hipError_t e = configure_dynamic_lds(k, lds, true);
+    if (e != hipSuccess) return e;
+    static bool reported = false;
+    if (!reported && std::getenv("ADX_OCC")) {   // diagnostic: resident workgroups per CU at this LDS size
         hipFuncAttributes fa;
-        hipError_t e = hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(k));
-        if (e != hipSuccess) return e;
-        if (fa.sharedSizeBytes != 0) return hipErrorInvalidKernelFile;
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
-        if (e != hipSuccess) return e;
-        if (std::getenv("ADX_OCC")) {   // diagnostic: resident workgroups per CU at this LDS size
-            int nb = 0;
-            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void *>(k), NWV * WAVE, lds);
-            std::fprintf(stderr, "mfe_pair_kernel<%d>: %d waves, %zu B LDS, %d VGPRs, %d workgroups per CU\n", NM,
-                         NWV, lds, fa.numRegs, nb);
-        }
-        configured = true;
+        int nb = 0;
+        (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(k));
+        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void *>(k), NWV * WAVE, lds);
+        std::fprintf(stderr, "mfe_pair_kernel<%d>: %d waves, %zu B LDS, %d VGPRs, %d workgroups per CU\n", NM,
+                     NWV, lds, fa.numRegs, nb);
     }
+    reported = true;
     hipLaunchKernelGGL(k, dim3(W * ka.n_groups2), dim3(NWV * WAVE), lds, stream, ka, ka.X, ka.T, seqs, W, gout, mask);
     return hipGetLastError();
 }

@@ -1,7 +1,7 @@
 // gfx950 outside pass (base-pair probabilities, SURVEY.md A16 / BASELINE
 // configs 3-4) with lanes = cells: the adjoint of the inside recursions of
-// kernels.hip pf_group, in gather form and descending span order -- the same
-// equations as kernels.hip outside() (oracle/fold.c orc_bppm is the scatter
+// fold_rows.hip pf_group, in gather form and descending span order -- the same
+// equations as fold_rows.hip outside() (oracle/fold.c orc_bppm is the scatter
 // form of the sweep), mapped the way mfe_cells.hip maps the MFE:
 //
 //   * one workgroup (16 waves) per (walker, unconstrained fold with pair
@@ -29,7 +29,7 @@
 //
 // Covered: unconstrained folds (the pair terms' folds are the conditions'
 // unconstrained folds, adx_api.cpp), N <= 112 (LDS); everything else takes
-// kernels.hip bppm_kernel.
+// fold_rows.hip bppm_kernel.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -38,6 +38,7 @@
 
 #include "dev_types.hpp"
 #include "fold_common.hpp"
+#include "launch.hpp"
 
 #ifndef MS_CH
 #define MS_CH 4   // terms per multiloop-sum read step (even; 16: 423k, 4: 430k, 2: 424k config-3 MC steps/s)
@@ -49,9 +50,6 @@ namespace adx {
 // Diagnostic build only: per-wave cycle sums of the phases (s_memtime), read
 // back through adx_debug_stamps_outside().  Never in the product.
 __device__ unsigned long long g_stamps_o[16][8];
-#define OSTAMP(k) do { __builtin_amdgcn_sched_barrier(0); const unsigned long long t_ = __builtin_amdgcn_s_memtime(); st_acc[k] += t_ - st_last; st_last = t_; __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define OSTAMP(k) do { } while (0)
 #endif
 }  // namespace adx
 
@@ -62,9 +60,6 @@ namespace adx {
 namespace {
 
 constexpr int OX_NMAX = 112;
-#ifndef OX_PART
-#define OX_PART 0   // interior-loop size partition of the B waves (A/B knob)
-#endif
 constexpr int OX_SLACK = 64;          // zeroed floats after each cell table (reads past a row end)
 
 // LDS carve for folded length N (runtime; the host sizes the launch with it)
@@ -150,11 +145,8 @@ outside_cells_kernel(KArgs ka, const DevScaled *__restrict__ XS, const uint8_t *
     // physical wave -> role: the finalize roles (0, 1) run on waves 2, 3 and the
     // finalize-record roles (2, 3) on waves 0, 1, so the finalize shares its SIMDs
     // with fewer multiloop-sum waves (config 3 462.5k -> 470.3k MC steps/s,
-    // profiles/r04zd_ab_wperm.txt; OX_WPERM overrides it in diagnostic builds)
-#ifndef OX_WPERM
-#define OX_WPERM 2, 3, 0, 1, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15
-#endif
-    constexpr int wperm[OX_NW] = {OX_WPERM};
+    // profiles/r04zd_ab_wperm.txt)
+    constexpr int wperm[OX_NW] = {2, 3, 0, 1, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15};
     const int tid = threadIdx.x, lane = tid & (WAVE - 1), wid = uni(wperm[tid / WAVE]);
     const int C = Y.C, NP = Y.NP;
 #ifdef ADX_STAMP
@@ -163,14 +155,14 @@ outside_cells_kernel(KArgs ka, const DevScaled *__restrict__ XS, const uint8_t *
 #endif
     const DevTables &T = *ka.T;
 
-    // ---- the proposal's inside tables (score_kernel's P = sp_score layout, kernels.hip Inc)
+    // ---- the proposal's inside tables (score_kernel's P = sp_score layout, fold_rows.hip Inc)
     const size_t B = 3 * size_t(ka.cells) + size_t(ka.Nmax) + 2;
     const size_t go = (sp_score == 2 ? size_t(ka.bvar_slot[bv]) : size_t(v)) * B;
     const int cur = ka.cur_slot[w];
     const float *src = ka.tab + size_t(w) * 2 * ka.tab_slot + size_t(1 - cur) * ka.tab_slot + go;
     const size_t Cs = size_t(ka.cells);   // the slot's table stride (Nmax cells)
 
-    // sequence (kernels.hip pf_group: contexts, ViennaRNA S1 wrap)
+    // sequence (fold_rows.hip pf_group: contexts, ViennaRNA S1 wrap)
     {
         const uint8_t *bef = nullptr, *aft = nullptr;
         int blen = 0;
@@ -203,7 +195,7 @@ outside_cells_kernel(KArgs ka, const DevScaled *__restrict__ XS, const uint8_t *
         const int u = k >> 5, n1 = k & 31, n2 = u - n1;
         float f = 0.f;
         if (n1 <= u) {
-            const int kd = okind(n1, n2);
+            const int kd = loop_kind(n1, n2);
             f = kd < 0 ? XS->fgen[(u - 6) * FG_ROW + n1 - 2]
               : kd == TK_STK ? XS->ctab[CT_FSM + 0]
               : kd == TK_B1 ? XS->ctab[CT_FSM + 1]
@@ -263,7 +255,7 @@ outside_cells_kernel(KArgs ka, const DevScaled *__restrict__ XS, const uint8_t *
     __syncthreads();
 
     OSTAMP(0);   // loads + table pass
-    // ---- exterior adjoint (kernels.hip outside(), push form, one wave, lanes = m):
+    // ---- exterior adjoint (fold_rows.hip outside(), push form, one wave, lanes = m):
     // once q5b[j] is known every m <= j-5 takes q5b[j] G(m+1, j).  acc[j-5] is
     // final after the push of j, and q5b[j-5] needs it four steps later, so the
     // loop-carried chain is one FMA: q5b[j-1] = sigma q5b[j] + acc[j-1], acc[j-1]
@@ -548,27 +540,11 @@ outside_cells_kernel(KArgs ka, const DevScaled *__restrict__ XS, const uint8_t *
             case 3: b_sweep<2, 3, 30, 6, 11, -1>(L, N, lane, std::integral_constant<int, 3>{}, fin OX_STP_ARGS); break;
             case 4: b_sweep<2, 29, 28, 27, 1, -1>(L, N, lane, std::integral_constant<int, 4>{}, fin OX_STP_ARGS); break;
             case 5: b_sweep<2, 26, 25, 24, 2, -1>(L, N, lane, std::integral_constant<int, 5>{}, fin OX_STP_ARGS); break;
-#if OX_PART == 1   // (A/B knobs) size 10 from block 8 to the record wave 7, size 9 from block 9 to block 6
-            case 6: b_sweep<2, 22, 21, 20, 8, 9>(L, N, lane, std::integral_constant<int, 6>{}, fin OX_STP_ARGS); break;
-            case 7: b_sweep<2, 10, -1, -1, -1, -1>(L, N, lane, std::integral_constant<int, 7>{}, fin OX_STP_ARGS); break;
-            case 8: b_sweep<2, 18, 17, 16, -1, -1>(L, N, lane, std::integral_constant<int, 8>{}, fin OX_STP_ARGS); break;
-            default: b_sweep<2, 14, 13, 12, -1, -1>(L, N, lane, std::integral_constant<int, 9>{}, fin OX_STP_ARGS); break;   // wave 9
-#elif OX_PART == 2   // size 10 from block 8 to the record wave 7
-            case 6: b_sweep<2, 22, 21, 20, 8, -1>(L, N, lane, std::integral_constant<int, 6>{}, fin OX_STP_ARGS); break;
-            case 7: b_sweep<2, 10, -1, -1, -1, -1>(L, N, lane, std::integral_constant<int, 7>{}, fin OX_STP_ARGS); break;
-            case 8: b_sweep<2, 18, 17, 16, -1, -1>(L, N, lane, std::integral_constant<int, 8>{}, fin OX_STP_ARGS); break;
-            default: b_sweep<2, 14, 13, 12, 9, -1>(L, N, lane, std::integral_constant<int, 9>{}, fin OX_STP_ARGS); break;   // wave 9
-#elif OX_PART == 3   // size 10 from block 8 to block 6
-            case 6: b_sweep<2, 22, 21, 20, 8, 10>(L, N, lane, std::integral_constant<int, 6>{}, fin OX_STP_ARGS); break;
-            case 7: b_sweep<2, -1, -1, -1, -1, -1>(L, N, lane, std::integral_constant<int, 7>{}, fin OX_STP_ARGS); break;
-            case 8: b_sweep<2, 18, 17, 16, -1, -1>(L, N, lane, std::integral_constant<int, 8>{}, fin OX_STP_ARGS); break;
-            default: b_sweep<2, 14, 13, 12, 9, -1>(L, N, lane, std::integral_constant<int, 9>{}, fin OX_STP_ARGS); break;   // wave 9
-#else
+            // (sizes 10 and 9 moved off blocks 8 / 9 measured within noise)
             case 6: b_sweep<2, 22, 21, 20, 8, -1>(L, N, lane, std::integral_constant<int, 6>{}, fin OX_STP_ARGS); break;
             case 7: b_sweep<2, -1, -1, -1, -1, -1>(L, N, lane, std::integral_constant<int, 7>{}, fin OX_STP_ARGS); break;
             case 8: b_sweep<2, 18, 17, 16, 10, -1>(L, N, lane, std::integral_constant<int, 8>{}, fin OX_STP_ARGS); break;
             default: b_sweep<2, 14, 13, 12, 9, -1>(L, N, lane, std::integral_constant<int, 9>{}, fin OX_STP_ARGS); break;   // wave 9
-#endif
         }
     } else for (int d = N - 1; d >= 3; d--) {
         const int nls = d >= 4 ? (N - d + WAVE - 1) / WAVE : 0;   // lane-sets of diagonal d
@@ -636,7 +612,7 @@ outside_cells_kernel(KArgs ka, const DevScaled *__restrict__ XS, const uint8_t *
         for (int k = 0; k < 8; k++) atomicAdd(&g_stamps_o[wid][k], st_acc[k]);
 #endif
     // ---- requested pairs of this fold (score terms), the motif's inner pairs credited
-    // from its closing cell (kernels.hip outside())
+    // from its closing cell (fold_rows.hip outside())
     double *pp = pair_p + size_t(w) * ka.n_pairs;
     for (int t = tid; t < ka.n_pairs; t += OX_NT) {
         if (ka.pairs[3 * t] != bv) continue;
@@ -663,20 +639,15 @@ outside_cells_kernel(KArgs ka, const DevScaled *__restrict__ XS, const uint8_t *
 size_t outside_cells_lds(const KArgs &ka) {
     if (ka.Nmax > OX_NMAX || ka.Nmax < 8 || ka.n_pairs > OX_MAXP || !ka.tab) return 0;
     const OxLay y(ka.Nmax);
-    return y.BYTES + 256 <= 160 * 1024 ? y.BYTES : 0;
+    return y.BYTES + 256 <= size_t(LDS_LIMIT) ? y.BYTES : 0;
 }
 
 hipError_t launch_outside_cells(const KArgs &ka, const uint8_t *seqs, int W, const int *mask, double *pair_p,
                                 int sp_score, hipStream_t stream) {
     const size_t lds = outside_cells_lds(ka);
     if (lds == 0) return hipErrorInvalidValue;
-    static size_t configured = 0;
-    if (lds > configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(outside_cells_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
-        if (e != hipSuccess) return e;
-        configured = lds;
-    }
+    hipError_t e = configure_dynamic_lds(outside_cells_kernel, lds);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(outside_cells_kernel, dim3(W * ka.n_bvars), dim3(OX_NT), lds, stream, ka, ka.X, seqs, W, mask,
                        pair_p, sp_score);
     return hipGetLastError();

@@ -13,9 +13,7 @@
 #include "dev_types.hpp"
 #include "fold_common.hpp"
 
-#ifndef OSTAMP
-#define OSTAMP(k) do { } while (0)
-#endif
+#define OSTAMP(k) ADX_STAMP_AT(k)   // fold_common.hpp
 
 namespace adx {
 namespace {
@@ -58,20 +56,6 @@ __device__ __forceinline__ int inv_colb(int k) {
     return j;
 }
 
-// interior-loop shape kinds (dev_types.hpp TermKind; -1 = generic)
-__host__ __device__ constexpr int okind(int n1, int n2) {
-    return (n1 == 0 && n2 == 0) ? TK_STK
-         : (n1 + n2 == 1) ? TK_B1
-         : (n1 == 0 || n2 == 0) ? TK_BUL
-         : (n1 == 1 && n2 == 1) ? TK_I11
-         : (n1 == 1 && n2 == 2) ? TK_I12
-         : (n1 == 2 && n2 == 1) ? TK_I21
-         : (n1 == 2 && n2 == 2) ? TK_I22
-         : ((n1 == 2 && n2 == 3) || (n1 == 3 && n2 == 2)) ? TK_M23
-         : (n1 == 1 || n2 == 1) ? TK_1N
-         : -1;
-}
-
 struct OxCell {                 // per lane: the inner pair (i, j) of every shape
     int i;
     float mmin, tau_in, mo_in, m23_in;
@@ -85,7 +69,7 @@ struct OxCell {                 // per lane: the inner pair (i, j) of every shap
 template <int U, int N1>
 __device__ __forceinline__ void oshape1(const OxL &L, const OxCell &c, const float *fv, const float *qw,
                                         const uint8_t *ow, int ty2, float &g, float &sp) {
-    constexpr int k = okind(N1, U - N1);
+    constexpr int k = loop_kind(N1, U - N1);
     const float v = qw[U - N1];
     if constexpr (k < 0) {
         g = fmaf(v, fv[N1], g);
@@ -170,9 +154,6 @@ struct OxSizeQ {
         }
     }
 };
-#ifndef ADX_SMALL_R0
-#define ADX_SMALL_R0 1   // sizes <= 5 on phase 0 only (the other phases' copies are discarded)
-#endif
 template <int U>
 struct OxBlk {   // the size's state in a B wave (sizes <= 5 whole in every lane)
     using T = typename std::conditional<(U <= 5), OxSize<U>, OxSizeQ<U>>::type;

@@ -18,20 +18,20 @@
 //     record sets, the multiloop items one per M wave.
 //
 // Covered: pf_ring contexts (unconstrained folds with pair terms, N <= the
-// LDS limit); kernels.hip chooses it with the inside kernel.
+// LDS limit); dispatch.hip chooses it with the inside kernel.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
 #include "dev_types.hpp"
 #include "fold_common.hpp"
+#include "launch.hpp"
 
 namespace adx {
 #ifdef ADX_STAMP
 // Diagnostic build only: per-wave cycle sums of the phases (s_memtime), read
 // back through adx_debug_stamps_outside_ring().  Never in the product.
 __device__ unsigned long long g_stamps_or[16][8];
-#define OSTAMP(k) do { __builtin_amdgcn_sched_barrier(0); const unsigned long long t_ = __builtin_amdgcn_s_memtime(); st_acc[k] += t_ - st_last; st_last = t_; __builtin_amdgcn_sched_barrier(0); } while (0)
 #endif
 }  // namespace adx
 
@@ -231,7 +231,7 @@ outside_ring_kernel(KArgs ka, const DevScaled *__restrict__ XS, const uint8_t *s
         const int u = k >> 5, n1 = k & 31, n2 = u - n1;
         float f = 0.f;
         if (n1 <= u) {
-            const int kd = okind(n1, n2);
+            const int kd = loop_kind(n1, n2);
             f = kd < 0 ? XS->fgen[(u - 6) * FG_ROW + n1 - 2]
               : kd == TK_STK ? XS->ctab[CT_FSM + 0]
               : kd == TK_B1 ? XS->ctab[CT_FSM + 1]
@@ -703,20 +703,15 @@ outside_ring_kernel(KArgs ka, const DevScaled *__restrict__ XS, const uint8_t *s
 size_t outside_ring_lds(const KArgs &ka) {
     if (ka.Nmax < OR_NMIN || ka.Nmax > OR_NMAX || ka.n_pairs > OX_MAXP) return 0;
     const OrLay y(ka.Nmax);
-    return y.BYTES + 256 <= 160 * 1024 ? y.BYTES : 0;
+    return y.BYTES + 256 <= size_t(LDS_LIMIT) ? y.BYTES : 0;
 }
 
 hipError_t launch_outside_ring(const KArgs &ka, const uint8_t *seqs, int W, const int *mask, double *pair_p,
                                hipStream_t stream) {
     const size_t lds = outside_ring_lds(ka);
     if (lds == 0 || !ka.tab || !ka.bvar_slot) return hipErrorInvalidValue;
-    static size_t configured = 0;
-    if (lds > configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(outside_ring_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
-        if (e != hipSuccess) return e;
-        configured = lds;
-    }
+    hipError_t e = configure_dynamic_lds(outside_ring_kernel, lds);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(outside_ring_kernel, dim3(W * ka.n_bvars), dim3(OX_NT), lds, stream, ka, ka.X, seqs, W, mask,
                        pair_p);
     return hipGetLastError();

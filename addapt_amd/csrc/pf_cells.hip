@@ -1,7 +1,7 @@
 // gfx950 McCaskill inside pass (the reference's scoring path, vrna_pf at
 // scoring.cc:58,65; BASELINE configs 3-5 and the PF bench) with lanes = cells
 // -- the same recursions, constraints, ligand motif and incremental folds as
-// kernels.hip pf_group<…, 2, SumProd> (oracle/fold.c orc_pf_energy), mapped
+// fold_rows.hip pf_group<…, 2, SumProd> (oracle/fold.c orc_pf_energy), mapped
 // the way outside_cells.hip maps the outside pass:
 //
 //   * one workgroup (14 waves) per (walker, group of the apo and holo
@@ -21,7 +21,7 @@
 //       R   the setup records of diagonal s+1 (wave 9), built in four
 //           stages a step apart.
 //
-// Covered: N <= 100 (LDS); longer folds take kernels.hip score_kernel.
+// Covered: N <= 100 (LDS); longer folds take fold_rows.hip score_kernel.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -30,6 +30,7 @@
 
 #include "dev_types.hpp"
 #include "fold_common.hpp"
+#include "launch.hpp"
 
 namespace adx {
 namespace {
@@ -39,10 +40,7 @@ typedef float f2 __attribute__((ext_vector_type(2)));
 #ifndef PX_NMW_CFG
 #define PX_NMW_CFG 4
 #endif
-#ifndef PX_NB_CFG
-#define PX_NB_CFG 8   // eight interior-loop waves (round 6: +1.2 % PF over seven, A/B r06f)
-#endif
-constexpr int PX_NB = PX_NB_CFG;      // interior-loop blocks (waves 0 .. PX_NB - 1)
+constexpr int PX_NB = 8;              // interior-loop blocks (waves 0 .. 7; round 6: +1.2 % PF over seven, A/B r06f)
 constexpr int PX_NMW = PX_NMW_CFG;    // qm item waves (PX_NB + 3 .. PX_NB + 2 + PX_NMW)
 constexpr int PX_M0 = PX_NB + 3;
 constexpr int PX_NW = PX_M0 + PX_NMW;
@@ -56,9 +54,6 @@ __host__ __device__ constexpr int px_mw(int w) {   // M wave index (0 = most ite
          : (w >= PX_M0 + 4 && w < PX_NW) ? w - PX_M0 : -1;
 }
 constexpr int PX_NMAX = 100;
-#ifndef PX_PART
-#define PX_PART 8   // interior-loop size partition of the eight blocks (pf_cells_kernel; 0: before r07g, A/B r07g-r07i)
-#endif
 #ifndef PX_ROLE_PRIO
 #define PX_ROLE_PRIO 2   // s_setprio of the role waves (M, F, Q, R) over the interior-loop waves
 #endif
@@ -126,34 +121,11 @@ struct PxL {
     int N, NP;
 };
 
-__device__ __forceinline__ bool px_allowed(const PxL &L, int i, int j) {   // kernels.hip allowed()
-    const int fi = L.flg[i], fj = L.flg[j];
-    if ((fi | fj) & 1) return false;
-    if ((fi & 2) || (fj & 4)) return false;
-    const int pi = L.ptn[i], pj = L.ptn[j];
-    if (pi) return pi == j;
-    if (pj) return pj == i;
-    return L.enc[i] == L.enc[j];
-}
-
-// interior-loop shape kinds (dev_types.hpp TermKind; -1 = generic)
-__host__ __device__ constexpr int pkind(int n1, int n2) {
-    return (n1 == 0 && n2 == 0) ? TK_STK
-         : (n1 + n2 == 1) ? TK_B1
-         : (n1 == 0 || n2 == 0) ? TK_BUL
-         : (n1 == 1 && n2 == 1) ? TK_I11
-         : (n1 == 1 && n2 == 2) ? TK_I12
-         : (n1 == 2 && n2 == 1) ? TK_I21
-         : (n1 == 2 && n2 == 2) ? TK_I22
-         : ((n1 == 2 && n2 == 3) || (n1 == 3 && n2 == 2)) ? TK_M23
-         : (n1 == 1 || n2 == 1) ? TK_1N
-         : -1;
-}
 // constant factor of shape (u, n1) (adx_api.cpp addS / fgen); dz = 0 in every
 // lane but not provably uniform, so the factors of a B wave's sizes live in
 // VGPRs (as SGPRs they spill to lane slots, one v_readlane per use)
 __device__ __forceinline__ float shape_factor(const DevScaled *XS, int u, int n1, int dz) {
-    const int kd = pkind(n1, u - n1);
+    const int kd = loop_kind(n1, u - n1);
     const float *p = kd < 0 ? XS->fgen + (u - 6) * FG_ROW + n1 - 2
                    : kd == TK_STK ? XS->ctab + CT_FSM + 0
                    : kd == TK_B1 ? XS->ctab + CT_FSM + 1
@@ -177,7 +149,7 @@ struct PxCell {              // per lane: the closing pair (i, i+s)
 template <int U, int N1, bool MK>
 __device__ __forceinline__ void pshape1(const PxL &L, const PxCell &c, const float *fv, const f2 *qb,
                                         const uint8_t *cc, uint32_t bits, f2 &g, f2 &sp) {
-    constexpr int k = pkind(N1, U - N1);
+    constexpr int k = loop_kind(N1, U - N1);
     constexpr int FI = N1 < U - N1 ? N1 : U - N1;
     f2 v = qb[N1];
     // constrained cell: shapes past its unpaired runs count 0 (bit N1 of the size's
@@ -290,13 +262,12 @@ struct PxSizeQ {
     }
 };
 
+#define PSTAMP(k) ADX_STAMP_AT(k)   // fold_common.hpp
 #ifdef ADX_STAMP
 __device__ unsigned long long g_stamps_p[16][12];
-#define PSTAMP(k) do { __builtin_amdgcn_sched_barrier(0); const unsigned long long t_ = __builtin_amdgcn_s_memtime(); st_acc[k] += t_ - st_last; st_last = t_; __builtin_amdgcn_sched_barrier(0); } while (0)
 #define PX_STP_PARAMS , unsigned long long *st_acc, unsigned long long &st_last
 #define PX_STP_ARGS , st_acc, st_last
 #else
-#define PSTAMP(k) do { } while (0)
 #define PX_STP_PARAMS
 #define PX_STP_ARGS
 #endif
@@ -306,9 +277,6 @@ __device__ unsigned long long g_stamps_p[16][12];
 // PxSizeQ (shapes spread over the phases), sizes <= 5 (the stack, 1x1..2x3
 // table loops) computed whole by every lane and counted once (phase 0).  The
 // four partials are summed by DPP and phase 0 writes the cell's natural slot.
-#ifndef ADX_SMALL_R0
-#define ADX_SMALL_R0 1   // sizes <= 5 on phase 0 only (the other phases' copies are discarded)
-#endif
 template <int U>
 struct PxBlk {   // the size's state in a B wave
     using T = typename std::conditional<(U < 0), PxSize<-1>, typename std::conditional<(U <= 5), PxSize<U>, PxSizeQ<U>>::type>::type;
@@ -506,7 +474,7 @@ pf_cells_kernel(KArgs ka, const DevScaled *__restrict__ XS, const uint8_t *seqs,
     const int C = Y.C, NP = Y.NP;
     const DevTables &T = *ka.T;
 
-    // ---- incremental fold state (kernels.hip score_sequence / Inc): this group's
+    // ---- incremental fold state (fold_rows.hip score_sequence / Inc): this group's
     // tables of the current sequence (src) and the proposal's (dst)
     const size_t Cs = size_t(ka.cells), B1 = 3 * Cs + size_t(ka.Nmax) + 2;
     const float *src = nullptr;
@@ -578,7 +546,7 @@ pf_cells_kernel(KArgs ka, const DevScaled *__restrict__ XS, const uint8_t *seqs,
         v_fl = cons[4 * NP + kp];
     }
 
-    // ---- sequence, constraint arrays, tables (kernels.hip pf_group setup): the stores
+    // ---- sequence, constraint arrays, tables (fold_rows.hip pf_group setup): the stores
     if (tid < NP) {
         L.S[tid] = (tid >= 1 && tid <= N) ? v_s : 0;
         L.up[tid] = v_up;
@@ -667,7 +635,7 @@ pf_cells_kernel(KArgs ka, const DevScaled *__restrict__ XS, const uint8_t *seqs,
             for (int k = lane; k < mL; k += WAVE) {
                 const int pk = mpt[k];
                 if (pk < 0) ok = ok && L.up[o + k] >= 1;
-                else if (pk > k) ok = ok && px_allowed(L, o + k, o + pk);
+                else if (pk > k) ok = ok && allowed(L, o + k, o + pk);
             }
             const bool all = __ballot(!ok) == 0;
             if (lane == 0) L.mat[o] = all ? 1 : 0;
@@ -717,7 +685,7 @@ pf_cells_kernel(KArgs ka, const DevScaled *__restrict__ XS, const uint8_t *seqs,
                 const int type = ptype(S[i], S[j]);
                 L.cc[od + i - 1] = uint8_t(rtype(type) * 25 + S[j + 1] * 5 + S[i - 1]);
                 if (inb) {
-                    pr = type != 0 && px_allowed(L, i, j);
+                    pr = type != 0 && allowed(L, i, j);
                     f2 init = f2{-0.f, -0.f};
                     float m1 = 0.f;
                     if (pr) {
@@ -828,7 +796,7 @@ pf_cells_kernel(KArgs ka, const DevScaled *__restrict__ XS, const uint8_t *seqs,
             const int oc = ty * 25 + si1 * 5 + sj1;
             const int A = Q.ab[k] & 255, Bq = Q.ab[k] >> 8;
             P.t11[k] = P.t12[k] = P.t21[k] = P.t22[k] = 0.f;
-            {   // kernels.hip load_chunk: the table factors of the 1x1..2x2 loops
+            {   // fold_rows.hip load_chunk: the table factors of the 1x1..2x2 loops
                 auto t2of = [&](int n1, int n2) { return (L.cc[off(D - 2 - n1 - n2, N) + i + n1] * 41) >> 10; };
                 if (umax >= 2) P.t11[k] = T.int11[ty][t2of(1, 1)][si1][sj1];
                 if (umax >= 3) {
@@ -894,107 +862,22 @@ pf_cells_kernel(KArgs ka, const DevScaled *__restrict__ XS, const uint8_t *seqs,
     if (wid == PX_WQ) qfac(4);
     const int s_end = N + 1;
     if (wid < PX_NB) {
-#if PX_NB_CFG == 8
-        // eight blocks (A/B, round 6): sizes 9, 14, 6, 13 of the four blocks the
-        // stamps showed busiest (profiles/r06e_pf_cells_stamps.txt) on an eighth wave
+        // eight blocks (round 6, A/B r06f: +1.2 % PF over seven): sizes 9, 14, 6 of
+        // the blocks the stamps showed busiest (profiles/r06e_pf_cells_stamps.txt)
+        // on an eighth wave.  The other sizes are hand-placed from the stamps:
+        // against blocks of about equal LDS cost, 16 sits on block 3, 15 on block
+        // 5, 0 on block 1 and 13 on block 2 (+2.4 % PF r07g,
+        // +1.0 % r07i; moving sizes back onto block 4 was no faster, A/B r07n)
         switch (wid) {
             case 0: pb_sweep<5, 22, 12, 11, -1>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-#if PX_PART != 5 && PX_PART < 8
-            case 1: pb_sweep<4, 21, 19, 10, -1>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-#endif
-#if PX_PART != 7 && PX_PART < 8
-            case 2: pb_sweep<3, 20, 18, 8, -1>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-#endif
-#if PX_PART == 1   // (A/B knobs) size 16 from block 4 to block 3
-            case 3: pb_sweep<28, 26, 1, 7, 16>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-            case 4: pb_sweep<29, 27, 0, -1, -1>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-            case 5: pb_sweep<30, 2, 17, -1, -1>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-            case 6: pb_sweep<24, 25, 23, 15, -1>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-#elif PX_PART == 2   // size 16 from block 4 to block 5
-            case 3: pb_sweep<28, 26, 1, 7, -1>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-            case 4: pb_sweep<29, 27, 0, -1, -1>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-            case 5: pb_sweep<30, 2, 17, 16, -1>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-            case 6: pb_sweep<24, 25, 23, 15, -1>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-#elif PX_PART == 3   // size 0 from block 4 to block 3
-            case 3: pb_sweep<28, 26, 1, 7, 0>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-            case 4: pb_sweep<29, 27, 16, -1, -1>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-            case 5: pb_sweep<30, 2, 17, -1, -1>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-            case 6: pb_sweep<24, 25, 23, 15, -1>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-#elif PX_PART == 5   // as 4, and size 0 from block 4 to block 1
-            case 1: pb_sweep<4, 21, 19, 10, 0>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-            case 3: pb_sweep<28, 26, 1, 7, 16>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-            case 4: pb_sweep<29, 27, -1, -1, -1>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-            case 5: pb_sweep<30, 2, 17, 15, -1>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-            case 6: pb_sweep<24, 25, 23, -1, -1>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-#elif PX_PART == 6   // size 16 from block 4 to block 5, size 15 from block 6 to block 3
-            case 3: pb_sweep<28, 26, 1, 7, 15>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-            case 4: pb_sweep<29, 27, 0, -1, -1>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-            case 5: pb_sweep<30, 2, 17, 16, -1>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-            case 6: pb_sweep<24, 25, 23, -1, -1>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-#elif PX_PART == 7   // as 4, and size 13 from block 7 to block 2
-            case 2: pb_sweep<3, 20, 18, 8, 13>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-            case 3: pb_sweep<28, 26, 1, 7, 16>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-            case 4: pb_sweep<29, 27, 0, -1, -1>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-            case 5: pb_sweep<30, 2, 17, 15, -1>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-            case 6: pb_sweep<24, 25, 23, -1, -1>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-#elif PX_PART == 8   // as 4, size 0 from block 4 to block 1 and size 13 from block 7 to block 2
             case 1: pb_sweep<4, 21, 19, 10, 0>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
             case 2: pb_sweep<3, 20, 18, 8, 13>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
             case 3: pb_sweep<28, 26, 1, 7, 16>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
             case 4: pb_sweep<29, 27, -1, -1, -1>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
             case 5: pb_sweep<30, 2, 17, 15, -1>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
             case 6: pb_sweep<24, 25, 23, -1, -1>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-#elif PX_PART == 9 || PX_PART == 10 || PX_PART == 11   // as 8, then 8 (9, 11) from block 2 and 15 (10, 11) from block 5 to block 4
-            case 1: pb_sweep<4, 21, 19, 10, 0>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-#if PX_PART == 10
-            case 2: pb_sweep<3, 20, 18, 8, 13>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-#else
-            case 2: pb_sweep<3, 20, 18, 13, -1>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-#endif
-            case 3: pb_sweep<28, 26, 1, 7, 16>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-#if PX_PART == 9
-            case 4: pb_sweep<29, 27, 8, -1, -1>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-            case 5: pb_sweep<30, 2, 17, 15, -1>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-#elif PX_PART == 10
-            case 4: pb_sweep<29, 27, 15, -1, -1>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-            case 5: pb_sweep<30, 2, 17, -1, -1>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-#else
-            case 4: pb_sweep<29, 27, 8, 15, -1>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-            case 5: pb_sweep<30, 2, 17, -1, -1>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-#endif
-            case 6: pb_sweep<24, 25, 23, -1, -1>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-#elif PX_PART == 4   // size 16 from block 4 to block 3, size 15 from block 6 to block 5
-            case 3: pb_sweep<28, 26, 1, 7, 16>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-            case 4: pb_sweep<29, 27, 0, -1, -1>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-            case 5: pb_sweep<30, 2, 17, 15, -1>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-            case 6: pb_sweep<24, 25, 23, -1, -1>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-#else
-            case 3: pb_sweep<28, 26, 1, 7, -1>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-            case 4: pb_sweep<29, 27, 16, 0, -1>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-            case 5: pb_sweep<30, 2, 17, -1, -1>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-            case 6: pb_sweep<24, 25, 23, 15, -1>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-#endif
-#if PX_PART == 7 || PX_PART >= 8
             default: pb_sweep<9, 14, 6, -1, -1>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-#else
-            default: pb_sweep<9, 14, 6, 13, -1>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-#endif
         }
-#else
-        switch (wid) {
-            // blocks of about equal LDS cost per lane-set (a size >= 6: 3 reads for
-            // its special shapes + one per 4 generic ones; the small sizes ~3 per shape)
-            // (round 5: 9, 13, 14 moved off the waves the stamps showed busiest,
-            // profiles/r05w_pf_cells_stamps.txt: +0.7 %, profiles/r05_ab r05x)
-            case 0: pb_sweep<5, 22, 12, 11, 9>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-            case 1: pb_sweep<4, 21, 19, 10, 14>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-            case 2: pb_sweep<3, 20, 18, 8, 6>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-            case 3: pb_sweep<28, 26, 1, 7, -1>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-            case 4: pb_sweep<29, 27, 16, 0, -1>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-            case 5: pb_sweep<30, 2, 17, -1, -1>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-            default: pb_sweep<24, 25, 23, 15, 13>(L, XS, N, lane, wid, constrained, s_end PX_STP_ARGS); break;
-        }
-#endif
     } else {
         // the M / F / Q / R chains set the step time; issue arbitration favours the
         // older (B) waves of the workgroup, so these run at a higher priority
@@ -1173,21 +1056,17 @@ pf_cells_kernel(KArgs ka, const DevScaled *__restrict__ XS, const uint8_t *seqs,
 // LDS bytes of the lanes = cells PF kernel for this workload (0: not covered)
 size_t pf_cells_lds(const KArgs &ka) {
     if (ka.mode != 0 || ka.Nmax > PX_NMAX || ka.Nmax < 8) return 0;
-    const size_t b = PxLay(ka.Nmax).BYTES;   // no static LDS (block_or, not __syncthreads_or)
-    return b <= 160 * 1024 ? b : 0;
+    const size_t b = PxLay(ka.Nmax).BYTES;   // no static LDS (block_or, not __syncthreads_or; checked at launch)
+    return b <= size_t(LDS_LIMIT) ? b : 0;
 }
 
 hipError_t launch_pf_cells(const KArgs &ka, const uint8_t *seqs, int W, const int *mask, float *gout,
                            hipStream_t stream) {
     const size_t lds = pf_cells_lds(ka);
     if (lds == 0) return hipErrorInvalidValue;
-    static size_t configured = 0;
-    if (lds > configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(pf_cells_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
-        if (e != hipSuccess) return e;
-        configured = lds;
-    }
+    // the carve addresses LDS from 0: no static LDS may precede the block
+    hipError_t e = configure_dynamic_lds(pf_cells_kernel, lds, true);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(pf_cells_kernel, dim3(W * ka.n_groups2), dim3(PX_NT), lds, stream, ka, ka.X, seqs, W, mask,
                        gout);
     return hipGetLastError();

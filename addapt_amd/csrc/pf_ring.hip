@@ -38,6 +38,7 @@
 
 #include "dev_types.hpp"
 #include "fold_common.hpp"
+#include "launch.hpp"
 
 namespace adx {
 namespace {
@@ -98,30 +99,8 @@ struct RgL {
 // ring position of diagonal D's first cell
 __device__ __forceinline__ int rgo(int D, int RS) { return (D % RG_RING) * RS; }
 
-__device__ __forceinline__ bool rg_allowed(const RgL &L, int i, int j) {   // kernels.hip allowed()
-    const int fi = L.flg[i], fj = L.flg[j];
-    if ((fi | fj) & 1) return false;
-    if ((fi & 2) || (fj & 4)) return false;
-    const int pi = L.ptn[i], pj = L.ptn[j];
-    if (pi) return pi == j;
-    if (pj) return pj == i;
-    return L.enc[i] == L.enc[j];
-}
-
-__host__ __device__ constexpr int rkind(int n1, int n2) {
-    return (n1 == 0 && n2 == 0) ? TK_STK
-         : (n1 + n2 == 1) ? TK_B1
-         : (n1 == 0 || n2 == 0) ? TK_BUL
-         : (n1 == 1 && n2 == 1) ? TK_I11
-         : (n1 == 1 && n2 == 2) ? TK_I12
-         : (n1 == 2 && n2 == 1) ? TK_I21
-         : (n1 == 2 && n2 == 2) ? TK_I22
-         : ((n1 == 2 && n2 == 3) || (n1 == 3 && n2 == 2)) ? TK_M23
-         : (n1 == 1 || n2 == 1) ? TK_1N
-         : -1;
-}
 __device__ __forceinline__ float rshape_factor(const DevScaled *XS, int u, int n1) {
-    const int kd = rkind(n1, u - n1);
+    const int kd = loop_kind(n1, u - n1);
     return kd < 0 ? XS->fgen[(u - 6) * FG_ROW + n1 - 2]
          : kd == TK_STK ? XS->ctab[CT_FSM + 0]
          : kd == TK_B1 ? XS->ctab[CT_FSM + 1]
@@ -144,7 +123,7 @@ struct RgCell {              // per lane: the closing pair (i, i+s)
 template <int U, int N1, bool MK>
 __device__ __forceinline__ void rshape1(const RgL &L, const RgCell &c, const float *fv, const float *qb,
                                         const uint8_t *cc, uint32_t bits, float &g, float &sp) {
-    constexpr int k = rkind(N1, U - N1);
+    constexpr int k = loop_kind(N1, U - N1);
     constexpr int FI = N1 < U - N1 ? N1 : U - N1;
     float v = qb[N1];
     if constexpr (MK) v *= float((bits >> N1) & 1u);
@@ -245,9 +224,6 @@ template <int U>
 struct RgBlk {
     using T = typename std::conditional<(U < 0), RgSize<-1>, typename std::conditional<(U <= 5), RgSize<U>, RgSizeQ<U>>::type>::type;
 };
-#ifndef ADX_SMALL_R0
-#define ADX_SMALL_R0 1   // sizes <= 5 on phase 0 only (the other phases' copies are discarded)
-#endif
 template <int U, bool MK>
 __device__ __forceinline__ void rg_run(const typename RgBlk<U>::T &z, const RgL &L, const RgCell &c, int s, int umax,
                                        int r, int ctb, float outer, float &g, float &sp, float &gs, float &sps) {
@@ -285,15 +261,14 @@ __device__ __forceinline__ float wave_sum_dpp(float v) {
     return __int_as_float(__builtin_amdgcn_readlane(b, 15)) + __int_as_float(__builtin_amdgcn_readlane(b, 31)) +
            __int_as_float(__builtin_amdgcn_readlane(b, 47)) + __int_as_float(__builtin_amdgcn_readlane(b, 63));
 }
+#define RSTAMP(k) ADX_STAMP_AT(k)   // fold_common.hpp
 #ifdef ADX_STAMP
 // Diagnostic build only: per-wave cycle sums of the phases (s_memtime), read
 // back through adx_debug_stamps_ring().  Never in the product.
 __device__ unsigned long long g_stamps_r[16][8];
-#define RSTAMP(k) do { __builtin_amdgcn_sched_barrier(0); const unsigned long long t_ = __builtin_amdgcn_s_memtime(); st_acc[k] += t_ - st_last; st_last = t_; __builtin_amdgcn_sched_barrier(0); } while (0)
 #define RG_STP_PARAMS , unsigned long long *st_acc, unsigned long long &st_last
 #define RG_STP_ARGS , st_acc, st_last
 #else
-#define RSTAMP(k) do { } while (0)
 #define RG_STP_PARAMS
 #define RG_STP_ARGS
 #endif
@@ -565,7 +540,7 @@ pf_ring_kernel(KArgs ka, const DevScaled *__restrict__ XS, const uint8_t *seqs, 
             for (int k = lane; k < mL; k += WAVE) {
                 const int pk = mpt[k];
                 if (pk < 0) ok = ok && L.up[o + k] >= 1;
-                else if (pk > k) ok = ok && rg_allowed(L, o + k, o + pk);
+                else if (pk > k) ok = ok && allowed(L, o + k, o + pk);
             }
             const bool all = __ballot(!ok) == 0;
             if (lane == 0) L.mat[o] = all ? 1 : 0;
@@ -632,7 +607,7 @@ pf_ring_kernel(KArgs ka, const DevScaled *__restrict__ XS, const uint8_t *seqs, 
             if (inb) {
                 const int j = i + D;
                 const int type = ptype(S[i], S[j]);
-                pr = type != 0 && rg_allowed(L, i, j);
+                pr = type != 0 && allowed(L, i, j);
                 L.q1[colb(j) + i - 1] = pr ? L.dt[DT_MLS + type * 25 + S[i - 1] * 5 + S[j + 1]] : 0.f;
             }
             const uint64_t m = __ballot(pr);
@@ -675,7 +650,7 @@ pf_ring_kernel(KArgs ka, const DevScaled *__restrict__ XS, const uint8_t *seqs, 
             const int type = ptype(S[i], S[j]);
             L.cc[ro + i - 1] = uint8_t(rtype(type) * 25 + S[j + 1] * 5 + S[i - 1]);
             if (i >= lo && i <= hi) {
-                const bool pr = type != 0 && rg_allowed(L, i, j);
+                const bool pr = type != 0 && allowed(L, i, j);
                 float init = -0.f;
                 if (pr) {
                     const int u = D - 1;
@@ -1053,7 +1028,7 @@ pf_ring_kernel(KArgs ka, const DevScaled *__restrict__ XS, const uint8_t *seqs, 
 size_t pf_ring_lds(const KArgs &ka) {
     if (ka.mode != 0 || ka.Nmax < RG_NMIN || ka.Nmax > RG_NMAX) return 0;
     const size_t b = RgLay(ka.Nmax).BYTES;
-    return b + 256 <= 160 * 1024 ? b : 0;
+    return b + 256 <= size_t(LDS_LIMIT) ? b : 0;
 }
 // floats of per-workgroup qb scratch a stateless launch needs
 size_t pf_ring_scratch_floats(const KArgs &ka, int W) {
@@ -1064,13 +1039,8 @@ hipError_t launch_pf_ring(const KArgs &ka, const uint8_t *seqs, int W, const int
                           float *qscr, hipStream_t stream) {
     const size_t lds = pf_ring_lds(ka);
     if (lds == 0 || (!ka.tab && !qscr)) return hipErrorInvalidValue;
-    static size_t configured = 0;
-    if (lds > configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(pf_ring_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
-        if (e != hipSuccess) return e;
-        configured = lds;
-    }
+    hipError_t e = configure_dynamic_lds(pf_ring_kernel, lds);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(pf_ring_kernel, dim3(W * 2 * ka.n_groups2), dim3(RG_NT), lds, stream, ka, ka.X, seqs, W, mask,
                        gout, qscr);
     return hipGetLastError();

@@ -1,7 +1,7 @@
 """GPU parity of the MFE fold mode (BASELINE config 2).
 
 The MFE is integer dcal/mol arithmetic on both sides (oracle/fold.c
-orc_mfe_energy; kernels.hip MinPlus, exact in FP32), so fold energies must be
+orc_mfe_energy; fold_rows.hip MinPlus, exact in FP32), so fold energies must be
 BIT-EXACT (float32 equality), including +inf for constraints no structure
 satisfies.  Scores are exp/log of those energies: equal to 1e-12 (the device
 and host libm may differ in the last ulp).  MC trajectories: positions, bases,

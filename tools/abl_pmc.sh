@@ -1,5 +1,5 @@
 #!/bin/bash
-# LDS counters of ablation builds (addapt_amd/_lib/ablate/lib_<v>.so): one
+# LDS counters of ablation builds (addapt_amd/_lib/ablate/lib_<v>.so, tools/build_variant.py): one
 # rocprofv3 pass per build with the LDS counters only, plus a short bench
 # (results of ablation builds are wrong by design: timing / counters only).
 # usage: tools/abl_pmc.sh <tag> <variant>...

@@ -17,7 +17,7 @@
 #   py:<name>:<script args>         a tools/ script (e.g. 'py:stamp_mfe:tools/pf_stamps.py 100 mfe';
 #                                   ADX_LIB=<.so> in the environment selects an ablate build)
 #   libs:<name>:<variants>:<bench.py args>    interleaved A/B of engine builds in
-#                                   addapt_amd/_lib/ablate/lib_<variant>.so (tools/build_ablate.sh)
+#                                   addapt_amd/_lib/ablate/lib_<variant>.so (tools/build_variant.py)
 set -e
 tag=${1:?tag}
 shift

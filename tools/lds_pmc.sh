@@ -1,6 +1,6 @@
 #!/bin/bash
 # One LDS-counter pass (bank conflicts, LDS-active cycles, LDS / VALU
-# instructions) of the default bench for each ablate build lib_<v>.so.
+# instructions) of the default bench for each variant build lib_<v>.so (tools/build_variant.py).
 # usage: tools/lds_pmc.sh <tag> <variant>...
 set -e
 tag=$1; shift

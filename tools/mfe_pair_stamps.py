@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-wave phase breakdown of mfe_pair_kernel (two diagonals per barrier) in
 MC steps (incremental refolds; diagnostic stamp build:
-ADX_LIB=addapt_amd/_lib/ablate/lib_stamp.so, tools/build_ablate.sh).
+ADX_LIB=addapt_amd/_lib/ablate/lib_stamp.so, tools/build_variant.py stamp=tree::-DADX_STAMP).
 usage: mfe_pair_stamps.py [N] [W] [steps]"""
 import ctypes as C
 import os

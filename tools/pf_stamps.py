@@ -19,7 +19,7 @@ L.adx_debug_stamps(buf, 1)
 eng.score_batch([tmpl])
 L.adx_debug_stamps(buf, 1)
 V = eng.info.n_variants
-# stamp ids (kernels.hip STAMP(k)): 10 loop top + qm1 pass, 0 descriptors + chunk 0,
+# stamp ids (fold_rows.hip STAMP(k)): 10 loop top + qm1 pass, 0 descriptors + chunk 0,
 # 6 q5, 5 qm items, 4 qb cells + finalize, 9 barrier
 cols = [(10, "top"), (0, "late"), (6, "q5"), (5, "qm"), (4, "qb"), (7, "prep"), (9, "barrier")]
 print("cycles per PF per wave (avg over %d variants)" % V)

@@ -14,7 +14,7 @@ import csv
 import json
 import sys
 
-# the fold kernels one score launch consists of (kernels.hip, mfe_cells.hip)
+# the fold kernels one score launch consists of (fold_rows.hip, mfe_cells.hip, ...)
 SCORE_KERNELS = ("score_kernel", "mfe_cells_kernel", "pf_cells_kernel")
 
 path = sys.argv[1]
