@@ -14,7 +14,9 @@
 //      qm1 = min(c + stem, qm1(i, j-1) + MLbase) (cell e1 takes cell e0's qm1
 //      from the same lane), the unpaired part of qm
 //      U(i, j) = min(qm1(i, j), U(i+1, j) + MLbase) (cell e1 takes U of row
-//      i+1 from the next lane), qm = min(split, U)
+//      i+1 from the next lane), qm = min(split, U).  A refold runs only the
+//      rows it rewrites and one ghost row above them, whose restored qm stands
+//      in for its U (see F below)
 //   B  interior-loop partials of diagonals d and d+1, loop sizes u >= 2
 //      (inner spans <= d-3: final a step earlier), one lane-set over the
 //      pairable cells of both; every block wave folds its partial into the
@@ -46,6 +48,10 @@ namespace adx {
 #define PSTAMP(k) ADX_STAMP_AT(k)   // fold_common.hpp
 #ifdef ADX_STAMP
 __device__ unsigned long long g_stamps_p[16][16];
+// the same sums as they stand after the early steps (span e0 = d - 2 has more than
+// 64 rows, so a fold from scratch finalizes in two lane-sets): the share of those
+// steps, which tells the wave that sets them
+__device__ unsigned long long g_stamps_pe[16][16];
 #endif
 
 namespace {
@@ -313,12 +319,15 @@ __device__ __forceinline__ bool pair_setup(const KArgs &ka, const DevScaled *__r
     u32 rod = 0, r5 = 0;   // the odd last cell of each table, q5's prefix
     if (incr) {
         const size_t Cs = size_t(ka.cells);
+        const size_t gap = Cs - size_t(2 * half);   // from a table's last pair of cells to the next table
 #pragma unroll
         for (int t = 0; t < RS; t++) {
             const int k = tid + t * NT;
             const int kk = k < 3 * half ? k : 0;
-            const int a = kk / half, c = kk - a * half;
-            rsv[t] = *reinterpret_cast<const uint2 *>(inc.src + a * Cs + 2 * c);
+            // pair kk of the three tables' pairs: table kk / half, found by comparing (a
+            // run-time division per load, and by zero at N <= 5, before)
+            const size_t o = size_t(2 * kk) + (kk >= half ? gap : 0) + (kk >= 2 * half ? gap : 0);
+            rsv[t] = *reinterpret_cast<const uint2 *>(inc.src + o);
         }
 #pragma unroll
         for (int t = 0; t < RC; t++) {
@@ -376,14 +385,15 @@ __device__ __forceinline__ bool pair_setup(const KArgs &ka, const DevScaled *__r
     const unsigned long long st_s25 = __builtin_amdgcn_s_memtime();   // motif scan done
 #endif
     if (incr) {   // the restore's stores (loads issued at the start)
-        const size_t Cs = size_t(ka.cells);
+        // qbm, qm and qm1 lie one table stride apart in LDS
+        static_assert(PLay<NM>::QM - PLay<NM>::QBM == PLay<NM>::QM1 - PLay<NM>::QM, "one stride between the tables");
+        const int gapl = int((PLay<NM>::QM - PLay<NM>::QBM) / 4) - 2 * half;
 #pragma unroll
         for (int t = 0; t < RS; t++) {
             const int k = tid + t * NT;
             if (k < 3 * half) {
-                const int a = k / half, c = k - a * half;
-                u32 *d = a == 0 ? L.qbm : a == 1 ? L.qm : L.qm1;
-                *reinterpret_cast<uint2 *>(d + 2 * c) = rsv[t];
+                const int o = 2 * k + (k >= half ? gapl : 0) + (k >= 2 * half ? gapl : 0);
+                *reinterpret_cast<uint2 *>(L.qbm + o) = rsv[t];
             }
         }
         if ((Crs & 1) && tid < 3) (tid == 0 ? L.qbm : tid == 1 ? L.qm : L.qm1)[Crs - 1] = rod;
@@ -571,8 +581,10 @@ __device__ __forceinline__ void mfe_pair_fold(const KArgs &ka, const DevScaled *
     const uint32_t aqm = lds_addr(L.qm), aqm1 = lds_addr(L.qm1), ae4 = lds_addr(L.e4);
     constexpr int L_WAVE = 1;           // (round 5: wave 1 +0.8 % over wave 4, A/B r05zn/r05zo) the lists two steps ahead (diagonals d+4, d+5) and their B records
     constexpr int Q_WAVE = 3;           // q5 of two columns (on the finalize wave: -2.1 %, A/B r06n)
-    constexpr int fw[2] = {F_WAVE, 6};  // finalize lane-sets 0, 1 (rows 1..64, 64..127): lane-set 1
-                                        // (spans < 38) rides on block wave 6
+    constexpr int fw[2] = {F_WAVE, 6};  // finalize lane-sets 0, 1 (the first 64 rows, the rest): lane-set 1
+                                        // (a fold from scratch at spans < 38; a refold whose row window
+                                        // is longer, i.e. both partners of an enforced pair changed)
+                                        // rides on block wave 6
     constexpr int mw[2] = {0, 2};       // the split parts of spans d, d+1
     constexpr int fls = fw[0] == wid ? 0 : (fw[1] == wid ? 1 : -1);
     const int NP2 = 2 * NP;
@@ -648,6 +660,10 @@ __device__ __forceinline__ void mfe_pair_fold(const KArgs &ka, const DevScaled *
 #endif
     int sl = 0;   // list slot of this step: step index % 3
     for (int d = 6; d - 3 <= N; d += 2) {
+#ifdef ADX_STAMP
+        if (N - (d - 2) <= 64 && N - (d - 4) > 64 && lane == 0 && wid < 16)   // the first late step
+            for (int k = 0; k < 16; k++) atomicAdd(&g_stamps_pe[wid][k], st_acc[k]);
+#endif
         const int sl1 = sl == 2 ? 0 : sl + 1, sl2 = sl1 == 2 ? 0 : sl1 + 1;
         PSTAMP(0);
         int nPP = 0;
@@ -661,20 +677,34 @@ __device__ __forceinline__ void mfe_pair_fold(const KArgs &ka, const DevScaled *
             __builtin_amdgcn_s_setprio(0);
         }
         PSTAMP(1);
-        // ---------------- F: finalize e0 = d-2 and e1 = d-1.  Lanes = rows i (all
-        // rows: the unpaired part U is kept for every cell); a lane-set spans 64 rows,
-        // consecutive lane-sets overlap by one row (lane 63 recomputes the next set's
-        // first row for its U and writes nothing), so no value crosses waves.
+        // ---------------- F: finalize e0 = d-2 and e1 = d-1.  Lanes = rows i, from
+        // row fr to row lr.  A fold from scratch: all rows.  A refold: the rows whose
+        // qm it rewrites (qlo(e1) .. qhi(e0); the qbm / qm1 band lies inside) and one
+        // ghost row m_hi + 3 above them, where the span has it.  The ghost writes no
+        // table cell: it hands the restored qm of its two cells down as their unpaired
+        // parts U.  That is exact: qm(r, j) = min(split(r, j), U(r, j)), and every split
+        // of (r, j) plus the MLbase of the unpaired rows below r is a split of the row
+        // that takes it (same right part, left part qm one row longer), so the band's
+        // qm = min(split, U) is the same with either (tests/test_qm_boundary.py).
+        // Rows above the ghost only carried U and are not run.  A lane-set spans 64
+        // rows, consecutive lane-sets overlap by one row (lane 63 recomputes the next
+        // set's first row for its U and writes nothing), so no value crosses waves;
+        // the window's last row is row R (no cell of span e1) or the ghost, so the
+        // last lane needs no neighbour.
         {
             const int e0 = d - 2, e1 = d - 1;
             const int R = N - e0;                                   // rows of span e0 (e1: R - 1)
-            const int Lf = R <= 64 ? 1 : (R - 1 + 62) / 63;
+            const int fr = qlo(e1);
+            const int lr = incr ? min(R, m_hi + 3) : R;
+            const int nr = lr - fr + 1;
+            const int Lf = nr <= 64 ? 1 : (nr - 1 + 62) / 63;
             if (e0 <= N - 1 && fls >= 0 && fls < Lf) {
                 __builtin_amdgcn_s_setprio(PRIO_ROLE);
-                const int i0 = 1 + fls * 63 + lane;
+                const int i0 = fr + fls * 63 + lane;
                 const bool own = lane < 63 || fls == Lf - 1;         // the overlap lane writes nothing
-                const bool rowA = i0 <= R, rowB = i0 <= R - 1;
-                const int i = rowA ? i0 : R;                         // every lane reads (batch)
+                const bool rowA = i0 <= lr, rowB = i0 <= min(lr, R - 1);
+                const int i = rowA ? i0 : lr;                        // every lane reads (batch)
+                const bool ghost = incr && i == m_hi + 3;
                 const int jA = i + e0;
                 const int ceA = off(e0, N) + i - 1, ceB = off(e1, N) + i - 1;
                 const int cmA = colb(jA) + i - 1, cmB = colb(jA + 1) + i - 1;
@@ -682,7 +712,7 @@ __device__ __forceinline__ void mfe_pair_fold(const KArgs &ka, const DevScaled *
                 const int s3 = max(e0 - 3, 3), s2 = max(e0 - 2, 3), s1 = max(e0 - 1, 3);
                 const int c3 = off(s3, N) + i, c2 = off(s2, N) + i, c1 = off(s1, N) + i;
                 u32 initA, cceA, stA, pqA, mlA, spA, upA, a0, a1, vS3, cS3, vS3b, cS3b, vS2, cS2, vS2b, cS2b, vS1, cS1;
-                u32 initB, cceB, stB, mlB, spB, b0, b1;
+                u32 initB, cceB, stB, mlB, spB, b0, b1, gqA, gqB;
                 uint32_t si, si1, sjm, sj, sjp, ui, ui1, ujA, ujB, djm, dj;
                 {
                     const uint32_t aq = U.aq, ac = U.ac;
@@ -732,6 +762,8 @@ __device__ __forceinline__ void mfe_pair_fold(const KArgs &ka, const DevScaled *
                         "ds_read_u8 %[ujB], %[aUj] offset:1\n"
                         "ds_read_u8 %[djm], %[aDj] offset:0\n"
                         "ds_read_u8 %[dj], %[aDj] offset:1\n"
+                        "ds_read_b32 %[gqA], %[gq]\n"
+                        "ds_read_b32 %[gqB], %[gq] offset:4\n"
                         "s_waitcnt lgkmcnt(0)"
                         : [initA] "=&v"(initA), [cceA] "=&v"(cceA), [stA] "=&v"(stA), [pqA] "=&v"(pqA), [mlA] "=&v"(mlA),
                           [spA] "=&v"(spA), [upA] "=&v"(upA), [a0] "=&v"(a0), [a1] "=&v"(a1), [initB] "=&v"(initB),
@@ -740,7 +772,7 @@ __device__ __forceinline__ void mfe_pair_fold(const KArgs &ka, const DevScaled *
                           [vS1] "=&v"(vS1), [cS3] "=&v"(cS3), [cS3b] "=&v"(cS3b), [cS2] "=&v"(cS2), [cS2b] "=&v"(cS2b),
                           [cS1] "=&v"(cS1), [si] "=&v"(si), [si1] "=&v"(si1), [sjm] "=&v"(sjm), [sj] "=&v"(sj),
                           [sjp] "=&v"(sjp), [ui] "=&v"(ui), [ui1] "=&v"(ui1), [ujA] "=&v"(ujA), [ujB] "=&v"(ujB),
-                          [djm] "=&v"(djm), [dj] "=&v"(dj)
+                          [djm] "=&v"(djm), [dj] "=&v"(dj), [gqA] "=&v"(gqA), [gqB] "=&v"(gqB)
                         : [qA] "v"(aq + uint32_t(ceA) * 4u), [kA] "v"(ac + uint32_t(ceA)),
                           [q1A] "v"(aqm1 + uint32_t(cmA) * 4u), [q1P] "v"(aqm1 + uint32_t(colb(jA - 1) + i - 1) * 4u),
                           [mA] "v"(mA), [sA] "v"(sA), [uA] "v"(uA), [pA] "v"(pA), [pst] "i"(NM * 4 + 8),
@@ -749,7 +781,8 @@ __device__ __forceinline__ void mfe_pair_fold(const KArgs &ka, const DevScaled *
                           [q3] "v"(aq + uint32_t(c3) * 4u), [q2] "v"(aq + uint32_t(c2) * 4u), [q1] "v"(aq + uint32_t(c1) * 4u),
                           [k3] "v"(ac + uint32_t(c3)), [k2] "v"(ac + uint32_t(c2)), [k1] "v"(ac + uint32_t(c1)),
                           [aSi] "v"(aS + uint32_t(i)), [aSj] "v"(aS + uint32_t(jA - 1)), [aUi] "v"(aU + uint32_t(i)),
-                          [aUj] "v"(aU + uint32_t(jA)), [aDj] "v"(aD + uint32_t(jA - 1))
+                          [aUj] "v"(aU + uint32_t(jA)), [aDj] "v"(aD + uint32_t(jA - 1)),
+                          [gq] "v"(aqm + uint32_t(rowb(i, N) + e0 - 4) * 4u)   // the ghost's qm(i, jA), qm(i, jA + 1)
                         : "memory");
                 }
 #ifdef ADX_STAMP_F
@@ -797,7 +830,7 @@ __device__ __forceinline__ void mfe_pair_fold(const KArgs &ka, const DevScaled *
                     q1A = pfin(f1);
                     if (own) L.qm1[cmA] = q1A;
                 }
-                const u32 UA = ui >= 1 ? pmin(q1A, padd(upA, mlbase)) : q1A;
+                const u32 UA = ghost ? gqA : (ui >= 1 ? pmin(q1A, padd(upA, mlbase)) : q1A);
                 // cell B (its qm1 predecessor (i, jA) is cell A of this lane)
                 u32 q1B = stB;
                 if (inB) {
@@ -818,7 +851,7 @@ __device__ __forceinline__ void mfe_pair_fold(const KArgs &ka, const DevScaled *
 #endif
                 // U of row i+1 in column jA+1 (span e0) is the next lane's cell A
                 const u32 UA1 = u32(__builtin_amdgcn_ds_bpermute((lane + 1) * 4, int(UA)));
-                const u32 UB = ui >= 1 ? pmin(q1B, padd(UA1, mlbase)) : q1B;
+                const u32 UB = ghost ? gqB : (ui >= 1 ? pmin(q1B, padd(UA1, mlbase)) : q1B);
                 if (own && rowA) {
                     L.colmin[(e0 & 3) * NP + jA] = UA;
                     L.part[(e0 & 3) * 2 * NP + i] = PINF;
@@ -1280,6 +1313,14 @@ extern "C" int adx_debug_stamps_pair(unsigned long long *out, int reset) {  // [
     if (reset) {
         static unsigned long long z[16][16] = {};
         if (hipMemcpyToSymbol(HIP_SYMBOL(adx::g_stamps_p), z, sizeof(z)) != hipSuccess) return 2;
+    }
+    return 0;
+}
+extern "C" int adx_debug_stamps_pair_early(unsigned long long *out, int reset) {  // [16][16]: the early steps' share
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(adx::g_stamps_pe), sizeof(adx::g_stamps_pe)) != hipSuccess) return 1;
+    if (reset) {
+        static unsigned long long z[16][16] = {};
+        if (hipMemcpyToSymbol(HIP_SYMBOL(adx::g_stamps_pe), z, sizeof(z)) != hipSuccess) return 2;
     }
     return 0;
 }
