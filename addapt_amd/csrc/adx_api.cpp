@@ -426,6 +426,7 @@ struct Problem {
     DevBuf<int> dChg;
     DevBuf<int> dOrder;          // launch order of a rescore's folds (KArgs::order, order_kernel)
     DevBuf<uint8_t> dCls;        // the folds' weight classes (KArgs::ocls, the proposals' or a rescore's)
+    DevBuf<int> dTrace;          // c / fm / fm1 scratch of mfe_trace_kernel, one launch chunk
     size_t tab_slot = 0;
     bool state_on = false;   // set for MC launches only (not for adx_score_batch)
     std::unique_ptr<DevTables> hT;
@@ -656,6 +657,17 @@ struct Problem {
         return ADX_OK;
     }
 
+    // MFE structures of W sequences (device codes) for one variant: W * variants[v].N
+    // chars and W energies to device buffers (mfe_trace.hip); touches no fold state
+    adx_status trace(const uint8_t *dseqs, int W, int v, char *dstruct, float *denergy) {
+        const KArgs ka = kargs();
+        const int chunk = mfe_trace_chunk(ka, W);
+        const size_t need = size_t(chunk) * mfe_trace_slice_ints(ka);
+        if (dTrace.n < need) HIP_TRY(dTrace.alloc(need));
+        HIP_TRY(launch_mfe_trace(ka, v, dseqs, W, dTrace.p, chunk, dstruct, denergy, stream));
+        return ADX_OK;
+    }
+
     // the per-walker buffers a fold of W walkers writes (grow-only)
     adx_status prepare(int W) {
         adx_status so = ensure_ovf(W);
@@ -761,9 +773,8 @@ extern "C" adx_status adx_fold_add_constraint(adx_fold *f, const char *db) {
     return ADX_OK;
 }
 
-// One fold of the compound f in mode 0 (partition function) or 1 (MFE).
-static adx_status fold_energy(adx_fold *f, int mode, float *energy, std::vector<double> *bpp = nullptr) {
-    Problem pb;
+// The one-variant problem the compound f currently describes, uploaded.
+static adx_status fold_problem(adx_fold *f, int mode, Problem &pb) {
     pb.mode = mode;
     pb.device = f->device;
     pb.P = &f->params->P;
@@ -786,8 +797,15 @@ static adx_status fold_energy(adx_fold *f, int mode, float *energy, std::vector<
     pb.ctx_off.assign(4, 0);
     pb.tmap.assign(1, DevTermMap{0, 0, 1, 0.0});
     pb.n_terms = 0;
-    s = pb.upload_all();
+    return pb.upload_all();
+}
+
+// One fold of the compound f in mode 0 (partition function) or 1 (MFE).
+static adx_status fold_energy(adx_fold *f, int mode, float *energy, std::vector<double> *bpp = nullptr) {
+    Problem pb;
+    adx_status s = fold_problem(f, mode, pb);
     if (s) return s;
+    const int N = static_cast<int>(f->seq.size());
     std::vector<uint8_t> codes = encode(f->seq);
     DevBuf<uint8_t> dseq;
     DevBuf<double> dsc;
@@ -852,6 +870,28 @@ extern "C" adx_status adx_fold_pf(adx_fold *f, float *energy) {
 extern "C" adx_status adx_fold_mfe(adx_fold *f, float *energy) {
     if (!f || !energy) return fail(ADX_EINVAL, "adx_fold_mfe: null argument");
     return fold_energy(f, 1, energy);
+}
+
+extern "C" adx_status adx_fold_mfe_structure(adx_fold *f, char *structure, float *energy) {
+    if (!f || !structure || !energy) return fail(ADX_EINVAL, "adx_fold_mfe_structure: null argument");
+    Problem pb;
+    adx_status s = fold_problem(f, 1, pb);
+    if (s) return s;
+    const size_t N = f->seq.size();
+    const std::vector<uint8_t> codes = encode(f->seq);
+    DevBuf<uint8_t> dseq;
+    DevBuf<char> dst;
+    DevBuf<float> de;
+    HIP_TRY(dseq.upload(codes.data(), codes.size(), pb.stream));
+    HIP_TRY(dst.alloc(N));
+    HIP_TRY(de.alloc(1));
+    s = pb.trace(dseq.p, 1, 0, dst.p, de.p);
+    if (s) return s;
+    HIP_TRY(hipMemcpyAsync(structure, dst.p, N, hipMemcpyDeviceToHost, pb.stream));
+    HIP_TRY(hipMemcpyAsync(energy, de.p, sizeof(float), hipMemcpyDeviceToHost, pb.stream));
+    HIP_TRY(hipStreamSynchronize(pb.stream));
+    structure[N] = 0;
+    return ADX_OK;
 }
 
 extern "C" adx_status adx_fold_bpp(adx_fold *f, int i, int j, double *prob) {
@@ -1538,6 +1578,46 @@ extern "C" adx_status adx_bppm_batch(adx_ctx *c, int W, const char *seqs, int co
     HIP_TRY(hipMemcpyAsync(probs, dfull.p, sizeof(double) * W * L * L, hipMemcpyDeviceToHost, pb.stream));
     HIP_TRY(hipStreamSynchronize(pb.stream));
     return ADX_OK;
+}
+
+// MFE structures of W device sequences for variant v, copied to the host
+static adx_status mfe_structures(adx_ctx *c, const char *who, const uint8_t *dseqs, int W, int v, char *structures,
+                                 float *energies) {
+    Problem &pb = c->pb;
+    if (pb.mode != ADX_FOLD_MFE)
+        return fail(ADX_EUNSUPPORTED, "%s: ADX_FOLD_MFE contexts only (a partition-function context holds no "
+                    "energies; use adx_fold_mfe_structure)", who);
+    if (v < 0 || v >= static_cast<int>(pb.variants.size()))
+        return fail(ADX_EINVAL, "%s: variant %d outside [0, %zu)", who, v, pb.variants.size());
+    const size_t L = size_t(pb.variants[v].N);
+    DevBuf<char> dst;
+    DevBuf<float> de;
+    HIP_TRY(dst.alloc(size_t(W) * L));
+    HIP_TRY(de.alloc(W));
+    adx_status s = pb.trace(dseqs, W, v, dst.p, de.p);
+    if (s) return s;
+    HIP_TRY(hipMemcpyAsync(structures, dst.p, size_t(W) * L, hipMemcpyDeviceToHost, pb.stream));
+    if (energies) HIP_TRY(hipMemcpyAsync(energies, de.p, sizeof(float) * W, hipMemcpyDeviceToHost, pb.stream));
+    HIP_TRY(hipStreamSynchronize(pb.stream));
+    return ADX_OK;
+}
+
+extern "C" adx_status adx_mfe_structure_batch(adx_ctx *c, int W, const char *seqs, int variant, char *structures,
+                                              float *energies) {
+    if (!c || W <= 0 || !seqs || !structures) return fail(ADX_EINVAL, "adx_mfe_structure_batch: bad argument");
+    Problem &pb = c->pb;
+    std::vector<uint8_t> codes(size_t(W) * pb.Nraw);
+    for (size_t k = 0; k < codes.size(); k++) codes[k] = static_cast<uint8_t>(base_code(seqs[k]));
+    DevBuf<uint8_t> dseq;
+    HIP_TRY(dseq.upload(codes.data(), codes.size(), pb.stream));
+    return mfe_structures(c, "adx_mfe_structure_batch", dseq.p, W, variant, structures, energies);
+}
+
+extern "C" adx_status adx_walkers_mfe_structures(adx_ctx *c, int variant, char *structures, float *energies) {
+    if (!c || !structures) return fail(ADX_EINVAL, "adx_walkers_mfe_structures: null argument");
+    if (c->pb.mode == ADX_FOLD_MFE && c->W <= 0)
+        return fail(ADX_ESTATE, "adx_walkers_mfe_structures before adx_walkers_init");
+    return mfe_structures(c, "adx_walkers_mfe_structures", c->cur_seq.p, c->W, variant, structures, energies);
 }
 
 extern "C" adx_status adx_score_batch(adx_ctx *c, int W, const char *seqs, double *scores,

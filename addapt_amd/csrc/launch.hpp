@@ -60,6 +60,12 @@ bool mfe_pair_covers(const KArgs &ka);
 hipError_t launch_mfe_pair(const KArgs &ka, const uint8_t *seqs, int W, float *gout, const int *mask,
                            hipStream_t stream);
 
+// ---- mfe_trace.hip: MFE structures (fill + traceback, one workgroup per sequence)
+size_t mfe_trace_slice_ints(const KArgs &ka);   // ints of HBM scratch per workgroup
+int mfe_trace_chunk(const KArgs &ka, int W);    // sequences per launch, so the scratch stays bounded
+hipError_t launch_mfe_trace(const KArgs &ka, int variant, const uint8_t *seqs, int W, int *scratch, int chunk,
+                            char *structures, float *energies, hipStream_t stream);
+
 // ---- pf_cells.hip, pf_ring.hip
 size_t pf_cells_lds(const KArgs &ka);
 hipError_t launch_pf_cells(const KArgs &ka, const uint8_t *seqs, int W, const int *mask, float *gout,

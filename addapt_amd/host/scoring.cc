@@ -73,6 +73,22 @@ double GpuRnaFold::macrostate_prob(string constraint) const {
     return std::exp((double(g_tot) - double(g_act)) / kT());
 }
 
+// vrna_mfe with backtracking on the fold compound macrostate_prob builds
+std::pair<string, double> GpuRnaFold::mfe_structure(string constraint) const {
+    adx_fold *raw = nullptr;
+    gpu::check(adx_fold_create(gpu::params(), seq_.c_str(), 0, gpu_, &raw));
+    gpu::FoldPtr f(raw);
+    if (aptamer_)
+        gpu::check(adx_fold_add_motif(f.get(), aptamer_->seq().c_str(), aptamer_->fold().c_str(),
+                                      kT() * std::log(aptamer_->affinity() / 1e6)));
+    if (!constraint.empty()) gpu::check(adx_fold_add_constraint(f.get(), constraint.c_str()));
+    string structure(seq_.size() + 1, '\0');
+    float e = 0.f;
+    gpu::check(adx_fold_mfe_structure(f.get(), &structure[0], &e));
+    structure.resize(seq_.size());
+    return {structure, double(e)};
+}
+
 // scoring.cc:37-51 (0-based, symmetric)
 double GpuRnaFold::base_pair_prob(int i, int j) const {
     const int n = static_cast<int>(seq_.size());

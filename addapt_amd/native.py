@@ -78,6 +78,7 @@ EXPORTS = [
     "adx_walkers_download", "adx_score_batch", "adx_variant_desc", "adx_walkers_export",
     "adx_walkers_import", "adx_walkers_import_after", "adx_walkers_export_on", "adx_set_temperature", "adx_bppm_batch",
     "adx_walkers_rescore",
+    "adx_fold_mfe_structure", "adx_mfe_structure_batch", "adx_walkers_mfe_structures",
 ]
 
 _lib = None
@@ -107,6 +108,10 @@ def lib():
         L.adx_fold_add_constraint.argtypes = [C.c_void_p, C.c_char_p]
         L.adx_fold_pf.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         L.adx_fold_mfe.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        L.adx_fold_mfe_structure.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_float)]
+        L.adx_mfe_structure_batch.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_int, C.c_char_p,
+                                              C.POINTER(C.c_float)]
+        L.adx_walkers_mfe_structures.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.POINTER(C.c_float)]
         L.adx_fold_bpp.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double)]
         L.adx_fold_free.argtypes = [C.c_void_p]
         L.adx_ctx_create.argtypes = [C.POINTER(RunDesc), C.POINTER(C.c_void_p)]
@@ -185,6 +190,7 @@ class Fold:
 
     def __init__(self, seq, with_bppm=False, params=None, device=0):
         self.params = params or default_params()
+        self.N = len(seq)
         self.ptr = C.c_void_p()
         _check(lib().adx_fold_create(self.params.ptr, _b(seq), int(with_bppm), device,
                                      C.byref(self.ptr)))
@@ -204,6 +210,13 @@ class Fold:
         g = C.c_float()
         _check(lib().adx_fold_mfe(self.ptr, C.byref(g)))
         return g.value
+
+    def mfe_structure(self):
+        """(energy kcal/mol, dot-bracket) of one minimum-free-energy structure."""
+        g = C.c_float()
+        buf = C.create_string_buffer(self.N + 1)
+        _check(lib().adx_fold_mfe_structure(self.ptr, buf, C.byref(g)))
+        return g.value, buf.value.decode()
 
     def bpp(self, i, j):
         p = C.c_double()
@@ -309,6 +322,33 @@ class Engine:
         _check(lib().adx_bppm_batch(self.ptr, W, buf, c, context,
                                     out.ctypes.data_as(C.POINTER(C.c_double))))
         return out.reshape(W, L, L)
+
+    def _variant_length(self, v):
+        """Folded (context-padded) length of variant v (a bad index is the engine's to report)."""
+        if not 0 <= v < self.info.n_variants:
+            return self.N
+        ctx = self.variant(v)[0]
+        return self.N + (sum(self._ctx_lens[ctx]) if ctx >= 0 else 0)
+
+    def _structures(self, W, L, call):
+        buf = C.create_string_buffer(W * L + 1)
+        e = np.zeros(W, np.float32)
+        _check(call(buf, e.ctypes.data_as(C.POINTER(C.c_float))))
+        raw = buf.raw[:W * L].decode()
+        return [raw[w * L:(w + 1) * L] for w in range(W)], e
+
+    def mfe_structures(self, seqs, variant):
+        """(dot-bracket strings, float32 energies) of the MFE structures of `seqs`
+        in fold variant `variant` (fold_mode="mfe" engines)."""
+        W = len(seqs)
+        seqbuf = b"".join(_b(s) for s in seqs)
+        return self._structures(W, self._variant_length(variant), lambda st, e: lib().adx_mfe_structure_batch(
+            self.ptr, W, seqbuf, variant, st, e))
+
+    def walker_structures(self, variant):
+        """The same for the walkers' current sequences."""
+        return self._structures(self.W, self._variant_length(variant), lambda st, e: lib().adx_walkers_mfe_structures(
+            self.ptr, variant, st, e))
 
     def walkers_init(self, seeds, seqs=None):
         W = len(seeds)

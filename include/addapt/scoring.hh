@@ -9,6 +9,7 @@
 #include <map>
 #include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "addapt/model.hh"
@@ -49,6 +50,10 @@ public:
     explicit GpuRnaFold(DeviceConstPtr device, AptamerConstPtr aptamer = nullptr, int gpu = 0);
     double base_pair_prob(int i, int j) const override;
     double macrostate_prob(string constraint) const override;
+    /// One minimum-free-energy structure (dot-bracket) and its energy in
+    /// kcal/mol, under an optional hard constraint; the aptamer motif counts as
+    /// in macrostate_prob.  All '.' and +inf when the constraint admits nothing.
+    std::pair<string, double> mfe_structure(string constraint = "") const;
 
 private:
     string seq_;

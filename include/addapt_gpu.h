@@ -82,8 +82,14 @@ adx_status adx_fold_pf(adx_fold *f, float *energy_kcal);
  * reference): minimum free energy (kcal/mol, float; integer dcal arithmetic;
  * +inf when the constraint admits no structure), with the ligand motif
  * entering as c(i,j) = min(c(i,j), round(100*(E_motif + bonus))) at every site
- * where the motif can form.  Energy only, no structure. */
+ * where the motif can form.  Energy only; adx_fold_mfe_structure adds the
+ * structure. */
 adx_status adx_fold_mfe(adx_fold *f, float *energy_kcal);
+/* vrna_mfe with backtracking: structure = strlen(seq)+1 bytes, NUL-terminated
+ * dot-bracket of one optimal structure (ties broken in a fixed order; a formed
+ * ligand motif appears as the motif's own fold); all '.' and +inf when the
+ * constraint admits no structure.  Filled and traced on the GPU. */
+adx_status adx_fold_mfe_structure(adx_fold *f, char *structure, float *energy_kcal);
 /* fc->exp_matrices->probs[fc->iindx[i] - j] with 1-based i < j (:47-50);
  * computed on first use with md.compute_bpp (:41-44). */
 adx_status adx_fold_bpp(adx_fold *f, int i, int j, double *prob);
@@ -268,6 +274,20 @@ adx_status adx_score_batch(adx_ctx *ctx, int n_walkers, const char *seqs, double
  * (scoring.cc:47-50).  context = 0 without contexts. */
 adx_status adx_bppm_batch(adx_ctx *ctx, int n_walkers, const char *seqs, int condition, int context,
                           double *probs);
+
+/* MFE structures of W sequences (W*N chars) for variant v (adx_variant_desc):
+ * structures = W*L chars (L = the variant's folded, context-padded length; no
+ * terminators), energies[W] (kcal/mol, optional) -- bit for bit the variant's
+ * column of adx_score_batch's dG.  ADX_FOLD_MFE contexts only (a partition-
+ * function context holds Boltzmann factors, not energies: ADX_EUNSUPPORTED;
+ * use adx_fold_mfe_structure there).  Walker state, the stored tables and the
+ * next step's results are not touched. */
+adx_status adx_mfe_structure_batch(adx_ctx *ctx, int n_walkers, const char *seqs, int variant,
+                                   char *structures, float *energies);
+
+/* The same for the walkers' current sequences, read on the device
+ * (ADX_ESTATE before adx_walkers_init). */
+adx_status adx_walkers_mfe_structures(adx_ctx *ctx, int variant, char *structures, float *energies);
 
 /* Variant v of the score: which (context, condition, macrostate or -1). */
 adx_status adx_variant_desc(const adx_ctx *ctx, int v, int *context, int *condition,
