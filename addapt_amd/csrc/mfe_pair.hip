@@ -658,6 +658,23 @@ __device__ __forceinline__ void mfe_pair_fold(const KArgs &ka, const DevScaled *
 #ifdef ADX_STAMP
     st_acc[8] = sst[0] + (st_last - st_sw0);   // setup + the sweep's prelude
 #endif
+    // ---- F's anchor and running values (the waves with a finalize lane-set; role F
+    // below).  A fold from scratch is a refold whose hull clamps nowhere.
+    const int mloF = incr ? m_lo : -4096, mhiF = incr ? m_hi : 4096;
+    static_assert(NM - 4 <= 2 * WAVE - 1, "two overlapping lane-sets reach every row from row 1");
+    static_assert(PLay<NM>::NP == NM + 2 && 4 * (NM + 2) * 4 < 65536, "slot strides as ds offsets");
+    int ab = 0;   // the anchor: lane 0 of lane-set 0 is row ab (0: not chosen yet)
+    int fd = 0;   // the step the values below stand for (0, or a step this wave sat out: none)
+    int oE0 = 0, oE1 = 0, oS1 = 0, oS2 = 0, oS3 = 0;   // uniform: off() of spans e0, e1, e0-1, e0-2, e0-3
+    uint32_t mS = 0, mM = 0;                           // uniform: split slots e0 % 6, (e0 + 4) % 6 (bytes)
+    uint32_t cW = 0;                                   // uniform: U slot e0 & 3 (bytes; the partials': twice that)
+    int fI = 0;                                        // per lane: the row,
+    uint32_t fSi = 0, fSi1 = 0, fUi = 0, fUi1 = 0;     //   S[i], S[i+1], up[i], up[i+1],
+    uint32_t fRq = 0;                                  //   the address of qm(i, i + 4) less 4 words,
+    uint32_t fJ4 = 0, fSj = 0, fQ1 = 0;                //   4 jA, the addresses of S[jA - 1] and qm1(i, jA - 1)
+    // (the finalize wave holding PRIO_ROLE through its whole sweep instead of around F
+    // measured -1.1 %: its loop top then takes issue slots from the block waves, which
+    // set the step once F is this short; profiles/fanchor_ab.txt)
     int sl = 0;   // list slot of this step: step index % 3
     for (int d = 6; d - 3 <= N; d += 2) {
 #ifdef ADX_STAMP
@@ -691,39 +708,68 @@ __device__ __forceinline__ void mfe_pair_fold(const KArgs &ka, const DevScaled *
         // set's first row for its U and writes nothing), so no value crosses waves;
         // the window's last row is row R (no cell of span e1) or the ghost, so the
         // last lane needs no neighbour.
-        {
+        //
+        // Lanes keep their rows: lane l of lane-set fls is row ab + 63 fls + l while
+        // the anchor ab holds, and is masked off (EXEC) outside the step's window
+        // [fr, lr].  The window only moves down (fr, lr never grow), so the anchor is
+        // the lowest row from which the lane-sets still reach lr: max(1, lr - 63) for a
+        // window of one lane-set, max(1, lr - 126) for a longer one, chosen at the first
+        // step and again only when fr falls below it -- never in a fold from scratch
+        // (fr = 1), at most once in a one-position refold (changed row >= 62).  Between
+        // re-anchors every address is last step's plus a delta: the spans' cell offsets
+        // and the ring slots are uniform shift registers, the lane's column and its qm1
+        // column base advance by adds, its row's bytes and qm base stay
+        // (tests/test_finalize_anchor_model.py restates all of it).
+        if constexpr (fls >= 0) {
             const int e0 = d - 2, e1 = d - 1;
             const int R = N - e0;                                   // rows of span e0 (e1: R - 1)
-            const int fr = qlo(e1);
-            const int lr = incr ? min(R, m_hi + 3) : R;
-            const int nr = lr - fr + 1;
-            const int Lf = nr <= 64 ? 1 : (nr - 1 + 62) / 63;
-            if (e0 <= N - 1 && fls >= 0 && fls < Lf) {
+            const int fr = max(1, mloF - 2 - e1);                   // qlo(e1)
+            const int lr = min(R, mhiF + 3);
+            if (e0 <= N - 1 && (ab == 0 || fr < ab)) {              // (re-)anchor: both F waves alike
+                ab = max(1, lr - (lr - fr < 64 ? 63 : 126));
+                fd = 0;
+            }
+            if (e0 <= N - 1 && (fls == 0 || lr - ab > 63)) {        // lane-set 1: only past row ab + 63
                 __builtin_amdgcn_s_setprio(PRIO_ROLE);
-                const int i0 = fr + fls * 63 + lane;
-                const bool own = lane < 63 || fls == Lf - 1;         // the overlap lane writes nothing
-                const bool rowA = i0 <= lr, rowB = i0 <= min(lr, R - 1);
-                const int i = rowA ? i0 : lr;                        // every lane reads (batch)
-                const bool ghost = incr && i == m_hi + 3;
-                const int jA = i + e0;
-                const int ceA = off(e0, N) + i - 1, ceB = off(e1, N) + i - 1;
-                const int cmA = colb(jA) + i - 1, cmB = colb(jA + 1) + i - 1;
-                // inner cells of the stack / bulge-1 shapes: spans e0-3, e0-2, e0-1
-                const int s3 = max(e0 - 3, 3), s2 = max(e0 - 2, 3), s1 = max(e0 - 1, 3);
-                const int c3 = off(s3, N) + i, c2 = off(s2, N) + i, c1 = off(s1, N) + i;
+                constexpr uint32_t NP4 = uint32_t(NM + 2) * 4u;      // a ring slot, a partial half (bytes)
+                const uint32_t aq = U.aq, ac = U.ac, aS = lds_addr(L.S);
+                if (fls == 1 || fd != d) {   // the slow path: the closed forms at (ab, d); lane-set 1 (a block
+                                             // wave, a few steps of a wide refold) keeps no state but ab
+                    fI = ab + fls * 63 + lane;
+                    const int ic = min(fI, N);                       // rows past N are never active
+                    fSi = L.S[ic], fSi1 = L.S[ic + 1], fUi = L.up[ic], fUi1 = L.up[ic + 1];
+                    fRq = aqm + uint32_t(rowb(fI, N) - 4) * 4u;
+                    const int jA = fI + e0;
+                    fJ4 = uint32_t(jA) * 4u;
+                    fSj = aS + uint32_t(jA - 1);
+                    fQ1 = aqm1 + uint32_t(colb(jA - 1) + fI - 1) * 4u;
+                    // inner cells of the stack / bulge-1 shapes: spans e0-1, e0-2, e0-3 (the
+                    // impossible span 3 stands in for the ones no shape reads yet)
+                    oE0 = off(e0, N), oE1 = off(e1, N);
+                    oS1 = off(max(e0 - 1, 3), N), oS2 = off(max(e0 - 2, 3), N), oS3 = off(max(e0 - 3, 3), N);
+                    mS = uint32_t(e0 % 6) * NP4, mM = uint32_t((e0 + 4) % 6) * NP4;
+                    cW = uint32_t(e0 & 3) * NP4;
+                    fd = d;
+                }
+                const int i = fI;
+                const uint32_t i4 = uint32_t(i) * 4u;
+                const uint32_t q1P = fQ1, q1A = q1P + (fJ4 - 20u), q1B = q1A + (fJ4 - 16u);   // colb(j+1) - colb(j) = j - 4
+                if (i >= fr && i <= lr) {
+                const bool own = lane < 63 || fls == 1 || lr - ab <= 63;   // the overlap lane writes nothing
+                const bool rowB = i <= R - 1;
+                const bool ghost = i == mhiF + 3;
+                const uint32_t qA = (aq + uint32_t(oE0 - 1) * 4u) + i4, qB = (aq + uint32_t(oE1 - 1) * 4u) + i4;
+                const uint32_t pA = (lds_addr(L.part) + 2u * cW) + i4;       // slot e0 & 3; e1 & 3 is the next
+                const uint32_t uW = (lds_addr(L.colmin) + cW) + fJ4;         // U(.., jA) of span e0; e1: the next slot
+                const uint32_t gq = fRq + uint32_t(e0) * 4u;                 // qm(i, jA), qm(i, jA + 1)
                 u32 initA, cceA, stA, pqA, mlA, spA, upA, a0, a1, vS3, cS3, vS3b, cS3b, vS2, cS2, vS2b, cS2b, vS1, cS1;
                 u32 initB, cceB, stB, mlB, spB, b0, b1, gqA, gqB;
-                uint32_t si, si1, sjm, sj, sjp, ui, ui1, ujA, ujB, djm, dj;
+                uint32_t sjm, sj, sjp, ujA, ujB, djm, dj;
+                const uint32_t si = fSi, si1 = fSi1, ui = fUi, ui1 = fUi1;
                 {
-                    const uint32_t aq = U.aq, ac = U.ac;
-                    const uint32_t pA = lds_addr(L.part) + uint32_t(((e0 & 3) * 2 * NP) + i) * 4u;
-                    const uint32_t pB = lds_addr(L.part) + uint32_t(((e1 & 3) * 2 * NP) + i) * 4u;
-                    const uint32_t mA = lds_addr(L.mla) + uint32_t(((e0 + 4) % 6) * NP + i + 1) * 4u;   // span e0-2
-                    const uint32_t mB = lds_addr(L.mla) + uint32_t(((e1 + 4) % 6) * NP + i + 1) * 4u;
-                    const uint32_t sA = lds_addr(L.mla) + uint32_t((e0 % 6) * NP + i) * 4u;
-                    const uint32_t sB = lds_addr(L.mla) + uint32_t((e1 % 6) * NP + i) * 4u;
-                    const uint32_t uA = lds_addr(L.colmin) + uint32_t(((e0 + 3) & 3) * NP + jA) * 4u;  // span e0-1
-                    const uint32_t aS = lds_addr(L.S), aU = lds_addr(L.up), aD = lds_addr(L.dn);
+                    const uint32_t mA = (lds_addr(L.mla) + mM + 4u) + i4;   // span e0-2 (slot (e0 + 4) % 6), row i + 1; e1-2: the next slot
+                    const uint32_t sA = (lds_addr(L.mla) + mS) + i4;        // slot e0 % 6; e1 % 6 is the next
+                    const uint32_t uA = (lds_addr(L.colmin) + 3u * NP4 - cW) + fJ4;   // span e0-1: slot (e0 + 3) & 3
                     asm volatile(
                         "ds_read_b32 %[initA], %[qA]\n"
                         "ds_read_u8 %[cceA], %[kA]\n"
@@ -737,10 +783,10 @@ __device__ __forceinline__ void mfe_pair_fold(const KArgs &ka, const DevScaled *
                         "ds_read_b32 %[initB], %[qB]\n"
                         "ds_read_u8 %[cceB], %[kB]\n"
                         "ds_read_b32 %[stB], %[q1B]\n"
-                        "ds_read_b32 %[mlB], %[mB]\n"
-                        "ds_read_b32 %[spB], %[sB]\n"
-                        "ds_read_b32 %[b0], %[pB]\n"
-                        "ds_read_b32 %[b1], %[pB] offset:%[pst]\n"
+                        "ds_read_b32 %[mlB], %[mA] offset:%[pst]\n"
+                        "ds_read_b32 %[spB], %[sA] offset:%[pst]\n"
+                        "ds_read_b32 %[b0], %[pA] offset:%[pst2]\n"
+                        "ds_read_b32 %[b1], %[pA] offset:%[pst3]\n"
                         "ds_read_b32 %[vS3], %[q3]\n"
                         "ds_read_b32 %[vS3b], %[q3] offset:4\n"
                         "ds_read_b32 %[vS2], %[q2]\n"
@@ -751,17 +797,14 @@ __device__ __forceinline__ void mfe_pair_fold(const KArgs &ka, const DevScaled *
                         "ds_read_u8 %[cS2], %[k2]\n"
                         "ds_read_u8 %[cS2b], %[k2] offset:1\n"
                         "ds_read_u8 %[cS1], %[k1]\n"
-                        "ds_read_u8 %[si], %[aSi]\n"
-                        "ds_read_u8 %[si1], %[aSi] offset:1\n"
+                        // S, up, dn lie NP bytes apart (the carve): one address, jA - 1 in S
                         "ds_read_u8 %[sjm], %[aSj] offset:0\n"
                         "ds_read_u8 %[sj], %[aSj] offset:1\n"
                         "ds_read_u8 %[sjp], %[aSj] offset:2\n"
-                        "ds_read_u8 %[ui], %[aUi]\n"
-                        "ds_read_u8 %[ui1], %[aUi] offset:1\n"
-                        "ds_read_u8 %[ujA], %[aUj]\n"
-                        "ds_read_u8 %[ujB], %[aUj] offset:1\n"
-                        "ds_read_u8 %[djm], %[aDj] offset:0\n"
-                        "ds_read_u8 %[dj], %[aDj] offset:1\n"
+                        "ds_read_u8 %[ujA], %[aSj] offset:%[ou0]\n"
+                        "ds_read_u8 %[ujB], %[aSj] offset:%[ou1]\n"
+                        "ds_read_u8 %[djm], %[aSj] offset:%[od0]\n"
+                        "ds_read_u8 %[dj], %[aSj] offset:%[od1]\n"
                         "ds_read_b32 %[gqA], %[gq]\n"
                         "ds_read_b32 %[gqB], %[gq] offset:4\n"
                         "s_waitcnt lgkmcnt(0)"
@@ -770,19 +813,16 @@ __device__ __forceinline__ void mfe_pair_fold(const KArgs &ka, const DevScaled *
                           [cceB] "=&v"(cceB), [stB] "=&v"(stB), [mlB] "=&v"(mlB), [spB] "=&v"(spB), [b0] "=&v"(b0),
                           [b1] "=&v"(b1), [vS3] "=&v"(vS3), [vS3b] "=&v"(vS3b), [vS2] "=&v"(vS2), [vS2b] "=&v"(vS2b),
                           [vS1] "=&v"(vS1), [cS3] "=&v"(cS3), [cS3b] "=&v"(cS3b), [cS2] "=&v"(cS2), [cS2b] "=&v"(cS2b),
-                          [cS1] "=&v"(cS1), [si] "=&v"(si), [si1] "=&v"(si1), [sjm] "=&v"(sjm), [sj] "=&v"(sj),
-                          [sjp] "=&v"(sjp), [ui] "=&v"(ui), [ui1] "=&v"(ui1), [ujA] "=&v"(ujA), [ujB] "=&v"(ujB),
-                          [djm] "=&v"(djm), [dj] "=&v"(dj), [gqA] "=&v"(gqA), [gqB] "=&v"(gqB)
-                        : [qA] "v"(aq + uint32_t(ceA) * 4u), [kA] "v"(ac + uint32_t(ceA)),
-                          [q1A] "v"(aqm1 + uint32_t(cmA) * 4u), [q1P] "v"(aqm1 + uint32_t(colb(jA - 1) + i - 1) * 4u),
-                          [mA] "v"(mA), [sA] "v"(sA), [uA] "v"(uA), [pA] "v"(pA), [pst] "i"(NM * 4 + 8),
-                          [qB] "v"(aq + uint32_t(ceB) * 4u), [kB] "v"(ac + uint32_t(ceB)),
-                          [q1B] "v"(aqm1 + uint32_t(cmB) * 4u), [mB] "v"(mB), [sB] "v"(sB), [pB] "v"(pB),
-                          [q3] "v"(aq + uint32_t(c3) * 4u), [q2] "v"(aq + uint32_t(c2) * 4u), [q1] "v"(aq + uint32_t(c1) * 4u),
-                          [k3] "v"(ac + uint32_t(c3)), [k2] "v"(ac + uint32_t(c2)), [k1] "v"(ac + uint32_t(c1)),
-                          [aSi] "v"(aS + uint32_t(i)), [aSj] "v"(aS + uint32_t(jA - 1)), [aUi] "v"(aU + uint32_t(i)),
-                          [aUj] "v"(aU + uint32_t(jA)), [aDj] "v"(aD + uint32_t(jA - 1)),
-                          [gq] "v"(aqm + uint32_t(rowb(i, N) + e0 - 4) * 4u)   // the ghost's qm(i, jA), qm(i, jA + 1)
+                          [cS1] "=&v"(cS1), [sjm] "=&v"(sjm), [sj] "=&v"(sj), [sjp] "=&v"(sjp), [ujA] "=&v"(ujA),
+                          [ujB] "=&v"(ujB), [djm] "=&v"(djm), [dj] "=&v"(dj), [gqA] "=&v"(gqA), [gqB] "=&v"(gqB)
+                        : [qA] "v"(qA), [kA] "v"((ac + uint32_t(oE0 - 1)) + uint32_t(i)), [q1A] "v"(q1A), [q1P] "v"(q1P),
+                          [mA] "v"(mA), [sA] "v"(sA), [uA] "v"(uA), [pA] "v"(pA), [pst] "i"(NP4), [pst2] "i"(2 * NP4),
+                          [pst3] "i"(3 * NP4), [qB] "v"(qB), [kB] "v"((ac + uint32_t(oE1 - 1)) + uint32_t(i)), [q1B] "v"(q1B),
+                          [q3] "v"((aq + uint32_t(oS3) * 4u) + i4), [q2] "v"((aq + uint32_t(oS2) * 4u) + i4),
+                          [q1] "v"((aq + uint32_t(oS1) * 4u) + i4), [k3] "v"((ac + uint32_t(oS3)) + uint32_t(i)),
+                          [k2] "v"((ac + uint32_t(oS2)) + uint32_t(i)), [k1] "v"((ac + uint32_t(oS1)) + uint32_t(i)),
+                          [aSj] "v"(fSj), [ou0] "i"(NM + 2 + 1), [ou1] "i"(NM + 2 + 2), [od0] "i"(2 * (NM + 2)),
+                          [od1] "i"(2 * (NM + 2) + 1), [gq] "v"(gq)
                         : "memory");
                 }
 #ifdef ADX_STAMP_F
@@ -813,10 +853,12 @@ __device__ __forceinline__ void mfe_pair_fold(const KArgs &ka, const DevScaled *
                 const u32 mlclA = padd(mlclosing, L.dt[DT_MLS + rtype(tyA) * 25 + sjm * 5 + si1]);
                 const u32 mlclB = padd(mlclosing, L.dt[DT_MLS + rtype(tyB) * 25 + sj * 5 + si1]);
                 const u32 mmiA = L.dt[DT_MMI + cceA], mmiB = L.dt[DT_MMI + cceB];
-                const bool inA = rowA && (!incr || (i >= clo(e0) && i <= chi(e0)));
-                const bool inB = rowB && e1 <= N - 1 && (!incr || (i >= clo(e1) && i <= chi(e1)));
+                // the band's rows of the two spans (clo .. chi; the window's rows have i <= R)
+                const bool inA = i >= mloF - 1 - e0 && i <= mhiF + 1;
+                const bool inB = rowB && e1 <= N - 1 && i >= mloF - 1 - e1 && i <= mhiF + 1;
+                auto st32 = [](uint32_t a, u32 v) { *lds_at<u32>(a) = v; };   // the batch's addresses serve the stores
                 // cell A
-                u32 q1A = stA;   // restored qm1 outside the band
+                u32 m1A = stA;   // restored qm1 outside the band
                 if (inA) {
                     const u32 prev = (e0 >= 5 && ujA >= 1) ? padd(pqA, mlbase) : INF16;
                     u32 f1 = prev;
@@ -824,52 +866,80 @@ __device__ __forceinline__ void mfe_pair_fold(const KArgs &ka, const DevScaled *
                         u32 c = pmin(initA, pack2(int(a0), int(a1)));
                         c = pmin(c, iA);
                         c = pfin(pmin(c, padd(mlA, mlclA)));
-                        if (own) L.qbm[ceA] = pfin(padd(c, mmiA));
+                        if (own) st32(qA, pfin(padd(c, mmiA)));
                         f1 = pmin(padd(c, stA), prev);
                     }
-                    q1A = pfin(f1);
-                    if (own) L.qm1[cmA] = q1A;
+                    m1A = pfin(f1);
+                    if (own) st32(q1A, m1A);
                 }
-                const u32 UA = ghost ? gqA : (ui >= 1 ? pmin(q1A, padd(upA, mlbase)) : q1A);
+                const u32 UA = ghost ? gqA : (ui >= 1 ? pmin(m1A, padd(upA, mlbase)) : m1A);
                 // cell B (its qm1 predecessor (i, jA) is cell A of this lane)
-                u32 q1B = stB;
+                u32 m1B = stB;
                 if (inB) {
-                    const u32 prev = (e1 >= 5 && ujB >= 1) ? padd(q1A, mlbase) : INF16;
+                    const u32 prev = (e1 >= 5 && ujB >= 1) ? padd(m1A, mlbase) : INF16;
                     u32 f1 = prev;
                     if (initB != MARK16) {
                         u32 c = pmin(initB, pack2(int(b0), int(b1)));
                         c = pmin(c, iB);
                         c = pfin(pmin(c, padd(mlB, mlclB)));
-                        if (own) L.qbm[ceB] = pfin(padd(c, mmiB));
+                        if (own) st32(qB, pfin(padd(c, mmiB)));
                         f1 = pmin(padd(c, stB), prev);
                     }
-                    q1B = pfin(f1);
-                    if (own) L.qm1[cmB] = q1B;
+                    m1B = pfin(f1);
+                    if (own) st32(q1B, m1B);
                 }
 #ifdef ADX_STAMP_F
                 PSTAMP(12);   // F: the cells' terms
 #endif
-                // U of row i+1 in column jA+1 (span e0) is the next lane's cell A
+                // U of row i+1 in column jA+1 (span e0) is the next lane's cell A (a window
+                // row below lr has its neighbour in the window: both lanes are on)
                 const u32 UA1 = u32(__builtin_amdgcn_ds_bpermute((lane + 1) * 4, int(UA)));
-                const u32 UB = ghost ? gqB : (ui >= 1 ? pmin(q1B, padd(UA1, mlbase)) : q1B);
-                if (own && rowA) {
-                    L.colmin[(e0 & 3) * NP + jA] = UA;
-                    L.part[(e0 & 3) * 2 * NP + i] = PINF;
-                    L.part[(e0 & 3) * 2 * NP + NP + i] = PINF;
-                    if (e0 <= N - 3 && (!incr || (i >= qlo(e0) && i <= qhi(e0))))
-                        L.qm[rowb(i, N) + e0 - 4] = pfin(pmin(e0 >= 9 ? spA : INF16, UA));
+                const u32 UB = ghost ? gqB : (ui >= 1 ? pmin(m1B, padd(UA1, mlbase)) : m1B);
+                if (own) {
+                    st32(uW, UA);
+                    st32(pA, u32(PINF));
+                    st32(pA + NP4, u32(PINF));
+                    if (e0 <= N - 3 && i >= mloF - 2 - e0 && i <= min(R, mhiF + 2))   // qlo(e0) .. qhi(e0)
+                        st32(gq, pfin(pmin(e0 >= 9 ? spA : INF16, UA)));
                 }
                 if (own && rowB && e1 <= N - 1) {
-                    L.colmin[(e1 & 3) * NP + jA + 1] = UB;
-                    L.part[(e1 & 3) * 2 * NP + i] = PINF;
-                    L.part[(e1 & 3) * 2 * NP + NP + i] = PINF;
-                    if (e1 <= N - 3 && (!incr || (i >= qlo(e1) && i <= qhi(e1))))
-                        L.qm[rowb(i, N) + e1 - 4] = pfin(pmin(e1 >= 9 ? spB : INF16, UB));
+                    st32(uW + NP4 + 4u, UB);
+                    st32(pA + 2u * NP4, u32(PINF));
+                    st32(pA + 3u * NP4, u32(PINF));
+                    if (e1 <= N - 3 && i >= mloF - 2 - e1 && i <= min(R - 1, mhiF + 2))   // qlo(e1) .. qhi(e1)
+                        st32(gq + 4u, pfin(pmin(e1 >= 9 ? spB : INF16, UB)));
                 }
-                __builtin_amdgcn_s_setprio(0);
 #ifdef ADX_STAMP_F
                 PSTAMP(13);   // F: U, the stores
 #endif
+                }
+#ifdef ADX_STAMP_F
+                {   // the sub-phase sums were advanced by the window's lanes only: every lane
+                    // (lane 0 reports) takes them from the first lane of the window
+                    const uint64_t on = __ballot(i >= fr && i <= lr);
+                    if (on != 0) {
+                        const int src = __ffsll((long long)on) - 1;
+                        auto from = [&](unsigned long long v) {
+                            const uint32_t lo = __builtin_amdgcn_readlane(uint32_t(v), src);
+                            const uint32_t hi = __builtin_amdgcn_readlane(uint32_t(v >> 32), src);
+                            return (unsigned long long)lo | ((unsigned long long)hi << 32);
+                        };
+                        st_acc[11] = from(st_acc[11]), st_acc[12] = from(st_acc[12]), st_acc[13] = from(st_acc[13]);
+                        st_last = from(st_last);
+                    }
+                }
+#endif
+                // the running values of the next step
+                if constexpr (fls == 0) {
+                fQ1 = q1B;                       // qm1(i, jA + 1): the predecessor column of step d + 2
+                fJ4 += 8u, fSj += 2u;
+                oS3 = oS1, oS2 = oE0, oS1 = oE1;
+                oE0 = oE1 + (N - e1), oE1 = oE0 + (N - e1 - 1);   // off(e + 1) = off(e) + N - e
+                mM = mS, mS = mS == 4u * NP4 ? 0u : mS + 2u * NP4;
+                cW ^= 2u * NP4;
+                fd = d + 2;
+                }
+                __builtin_amdgcn_s_setprio(0);
             }
         }
         PSTAMP(2);
