@@ -149,10 +149,7 @@ hipError_t launch_score_m(const KArgs &ka, const uint8_t *seqs, int W, double *s
         kf.tab = nullptr;
         // overflows are rare: one block per CU scans the flags (ovf) instead of W
         // blocks that mostly exit at once
-#ifndef ADX_FB_GRID
-#define ADX_FB_GRID 64
-#endif
-        constexpr int FB_GRID = ADX_FB_GRID;
+        constexpr int FB_GRID = 64;
         return launch_score_rows(rows_lockstep(ka) == 2 ? RowsK::MinPlusP2 : RowsK::MinPlus512, kf, seqs, W, scores,
                                  terms, dG, ka.ovf, stream, FB_GRID);
     }

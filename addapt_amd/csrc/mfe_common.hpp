@@ -1,8 +1,12 @@
-// Helpers shared by the lanes = cells MFE kernels (mfe_cells.hip: one
-// anti-diagonal per barrier; mfe_pair.hip: two): the packed 16-bit min-plus
-// encoding (apo | holo halves), wave reductions, the LDS address of an object
-// and the per-lane state the generated interior-loop blocks (mfe_blocks.inc,
-// mfe_pair_blocks.inc; tools/gen_mfe_blocks.py) read.
+// What the lanes = cells MFE kernels share (mfe_cells.hip: one anti-diagonal
+// per barrier; mfe_pair.hip: two): the packed 16-bit min-plus encoding (apo |
+// holo halves), wave reductions, the LDS address of an object, the state the
+// generated interior-loop blocks (mfe_blocks.inc, mfe_pair_blocks.inc;
+// tools/gen_mfe_blocks.py) read and a B cell's setup for them, the carve
+// constants and byte arrays, a refold's band and slots, and the pieces of the
+// setup, write-back and epilogue that are the same in both.  The helpers take
+// either carve (CL, CP) as a template argument: the member names agree.  Where
+// the kernels differ in substance the code stays in the kernel's file.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -73,11 +77,7 @@ __device__ __forceinline__ T *lds_at(size_t a) {
 // space: uniform loads from it are scalar (s_load, lgkmcnt).  Through a generic
 // pointer they were flat loads, which count on vmcnt too, so the first record
 // use of a block waited for the block's 1x1..2x2 table prefetches from L2.
-#ifndef ADX_KFLAT
 typedef __attribute__((address_space(4))) const uint32_t kc_u32;
-#else   // A/B knob: the records through a generic pointer (flat loads), as before round 6
-typedef const uint32_t kc_u32;
-#endif
 __device__ __forceinline__ const kc_u32 *kconst(const uint4 *p) { return (const kc_u32 *)(uintptr_t)p; }
 __device__ __forceinline__ uint4 kload(const kc_u32 *p, int k) {   // record k (4 words)
     return make_uint4(p[4 * k], p[4 * k + 1], p[4 * k + 2], p[4 * k + 3]);
@@ -114,6 +114,244 @@ struct Acc {
 };
 
 #define MFE_SCHED_BARRIER() __builtin_amdgcn_sched_barrier(0)
+
+// wave-uniform part of the blocks' state (d, umax, mk: per step / lane-set)
+template <class LT>
+__device__ __forceinline__ BUni buni(const LT &L, const DevScaled *XS, int N) {
+    const u32 *gct = reinterpret_cast<const u32 *>(XS->ctab);
+    BUni U;
+    U.qbm = L.qbm;
+    U.cc = L.cc;
+    U.ct = L.ct;
+    U.gct = gct;
+    U.kg = reinterpret_cast<const uint4 *>(XS->ku16);
+    U.aq = lds_addr(L.qbm);
+    U.ac = lds_addr(L.cc);
+    U.act = lds_addr(L.ct);
+    U.fs1 = gct[CT_FSM + 1];
+    U.il = reinterpret_cast<const u32 *>(XS->il);
+    U.nin = reinterpret_cast<const u32 *>(XS->nin);
+    U.N = N;
+    return U;
+}
+
+// A B cell's setup: the closing pair's row, its code oc = type * 25 + S[i+1] * 5
+// + S[j-1], the unpaired runs inside it, mismatchI(oc) and mismatch1n(oc) +
+// mismatchI(oc).  The list role records it for the ranks < 64 (brec_word; the
+// kernels store the two energies their own way: three words a record in
+// mfe_cells.hip, two in mfe_pair.hip, which packs one half of each)
+struct BRec {
+    int i, oc, A, B;
+    u32 mmo, mo;
+};
+__device__ __forceinline__ u32 brec_word(int i, int oc, int A, int B) {   // the record's first word
+    return uint32_t(i) | (uint32_t(oc) << 8) | (uint32_t(A) << 16) | (uint32_t(B) << 24);
+}
+__device__ __forceinline__ BRec brec_unpack(u32 wd, u32 mmo, u32 mo) {
+    return BRec{int(wd & 255), int((wd >> 8) & 255), int((wd >> 16) & 255), int(wd >> 24), mmo, mo};
+}
+template <class LT>
+__device__ __forceinline__ int brec_code(const LT &L, int i, int j) {
+    return ptype(L.S[i], L.S[j]) * 25 + L.S[i + 1] * 5 + L.S[j - 1];
+}
+template <class LT>
+__device__ __forceinline__ BRec brec_of(const LT &L, int i, int j) {   // from the tables (ranks >= 64)
+    BRec r;
+    r.i = i;
+    r.oc = brec_code(L, i, j);
+    r.A = L.up[i + 1];
+    r.B = L.dn[j - 1];
+    r.mmo = L.dt[DT_MMI + r.oc];
+    r.mo = padd(L.ct[CT_ONEN + r.oc], r.mmo);
+    return r;
+}
+
+// lane slice r of 1 << sh per cell.  Edge shapes (gen_mfe_blocks.py
+// sliced_parts): 4 slices -> bulge (0,u), (u,0), 1 x n (1,u-1), (u-1,1);
+// 2 slices -> bulge (0,u) + 1 x n (1,u-1) or bulge (u,0) + 1 x n (u-1,1)
+__device__ __forceinline__ void bcell_slice(BCell &C, int r, int sh, uint32_t ae4) {
+    C.rs = uint32_t(r) * 4u;
+    C.ee = ae4 + uint32_t(r) * 4u;
+    C.r1 = (r & 1) != 0;
+    C.r2 = (r & 2) != 0;
+    C.eb = r & 1;
+    C.ea = sh == 2 ? ((r & 1) ? -(r >> 1) : (r >> 1)) : ((r & 1) ? -1 : 1);
+    C.ctb = (r & 2) ? CT_ONEN : CT_BUL;
+}
+
+// 1x1 .. 2x2 energies of cell (i, i + dd) from HBM (L2), used at the block end (the caller starts
+// them at INF16); p2, p3, p4: this wave's block reads loop size 2, 3, 4, um: the cell's largest.
+// mfe_pair.hip only: mfe_cells.hip tests one bit per block and keeps its copy (this form: -1.9 % at N = 150)
+template <class LT>
+__device__ __forceinline__ void bcell_tables(BCell &C, const LT &L, const DevTables &T, int N, int dd, int i, int oc,
+                                             int um, bool p2, bool p3, bool p4) {
+    const u32 *T11 = reinterpret_cast<const u32 *>(&T.int11[0][0][0][0]);
+    const u32 *T21 = reinterpret_cast<const u32 *>(&T.int21[0][0][0][0][0]);
+    const u32 *T22 = reinterpret_cast<const u32 *>(&T.int22[0][0][0][0][0][0]);
+    const int type = (oc * 41) >> 10, ty8 = type * 8;
+    const int si1 = (oc / 5) % 5, sj1 = oc % 5;
+    if (p2 && um >= 2) {
+        const int c2 = L.cc[off(dd - 4, N) + i + 1];
+        C.t11 = T11[((ty8 + ((c2 * 41) >> 10)) * 5 + si1) * 5 + sj1];
+    }
+    if (p3 && um >= 3) {
+        const int o3 = off(dd - 5, N) + i;
+        const int a2 = L.cc[o3 + 1], b2 = L.cc[o3 + 2];
+        const int ta = (a2 * 41) >> 10, tb = (b2 * 41) >> 10;
+        // 1x2: int21[type][t2][si1][sq1][sj1]; 2x1: int21[t2][type][sq1][si1][sp1]
+        C.t12 = T21[(((ty8 + ta) * 5 + si1) * 5 + (a2 / 5) % 5) * 5 + sj1];
+        C.t21 = T21[(((tb * 8 + type) * 5 + (b2 / 5) % 5) * 5 + si1) * 5 + b2 % 5];
+    }
+    if (p4 && um >= 4) {
+        const int c2 = L.cc[off(dd - 6, N) + i + 2];
+        const int t2 = (c2 * 41) >> 10;
+        // int22[type][t2][si1][sp1][sq1][sj1]
+        C.t22 = T22[((((ty8 + t2) * 5 + si1) * 5 + c2 % 5) * 5 + (c2 / 5) % 5) * 5 + sj1];
+    }
+}
+
+// a block's accumulators to the cell's partial minimum: the outer pair's terms,
+// then the minimum over the cell's lane slices
+__device__ __forceinline__ u32 acc_fold(const Acc &a, const BCell &C, int sh, u32 mmo, u32 mo, u32 tau) {
+    u32 acc = pmin(pmin(a.s, padd(pmin(a.g0, a.g1), mmo)), pmin(padd(a.b, tau), padd(a.n, mo)));
+    if (sh == 2) acc = pmin(acc, padd(a.e, C.r2 ? mo : tau));
+    if (sh == 2) acc = fold_rows16(acc);
+    if (sh >= 1) acc = fold_halves(acc);
+    return acc;
+}
+
+// ---------------------------------------------------------------- shared by both carves
+constexpr int NWV = 8;            // waves per walker
+constexpr int MFE_WPE = (2 * NWV + 3) / 4;   // waves per SIMD the register budget is cut for (2 workgroups)
+constexpr int MFE_E4_MAX = 64;    // slots of e4 the carves hold (MFE_E4_SLOTS of the generated blocks)
+constexpr size_t al16(size_t b) { return (b + 15) & ~size_t(15); }
+__device__ __forceinline__ int lanesets(int n) { return (n + 63) >> 6; }   // of a diagonal with n cells
+
+// The eight byte arrays, NP bytes apart from y in this order.  Role F's read
+// batch in mfe_pair.hip relies on the spacing: it reads up and dn at offsets
+// NP and 2 NP from an address in S
+template <class LT>
+__device__ __forceinline__ void carve_bytes(LT &l, uint8_t *y, int NP) {
+    l.S = y;
+    l.up = y + NP;
+    l.dn = y + 2 * NP;
+    l.ptn = y + 3 * NP;
+    l.enc = y + 4 * NP;
+    l.flg = y + 5 * NP;
+    l.mat = y + 6 * NP;
+    l.raw = y + 7 * NP;
+}
+
+// The band of a refold after positions m_lo .. m_hi changed: rows clo .. chi of
+// span dd hold the cells of qbm / qm1 that contain a changed position (or the
+// neighbour whose dangle they read), rows qlo .. qhi of span s the cells of qm
+// that do.  A fold from scratch: every row
+struct Band {
+    bool incr;
+    int N, m_lo, m_hi;
+    __device__ __forceinline__ int clo(int dd) const { return incr ? max(1, m_lo - 1 - dd) : 1; }
+    __device__ __forceinline__ int chi(int dd) const { return incr ? min(N - dd, m_hi + 1) : N - dd; }
+    __device__ __forceinline__ int qlo(int s) const { return incr ? max(1, m_lo - 2 - s) : 1; }
+    __device__ __forceinline__ int qhi(int s) const { return incr ? min(N - s, m_hi + 2) : N - s; }
+};
+
+// A fold's incremental state (KArgs::tab): the slot it writes and, for a
+// refold, the slot it restores and the changed positions in the folded sequence
+struct IncM {
+    const u32 *src;
+    u32 *dst;
+    int m_lo, m_hi;
+    const uint4 *cc_src;   // the slots' per-cell codes (dev_types.hpp inc_cc_offset); mfe_cells.hip
+    uint4 *cc_dst;         // recomputes the codes and leaves cc_src null
+    __device__ __forceinline__ Band band(int N) const { return Band{src != nullptr, N, uni(m_lo), uni(m_hi)}; }
+};
+// walker w's fold group g writes slot 1 - cur ...
+__device__ __forceinline__ IncM inc_slots(const KArgs &ka, int w, int g, int cur) {
+    const size_t Gf = inc_group_floats(ka.cells, ka.Nmax, 1);
+    float *to = ka.tab + size_t(w) * 2 * ka.tab_slot + size_t(1 - cur) * ka.tab_slot;
+    return IncM{nullptr, reinterpret_cast<u32 *>(to + size_t(g) * Gf), 0, 0, nullptr,
+                reinterpret_cast<uint4 *>(to + inc_cc_offset(ka.cells, ka.Nmax, ka.n_groups2, g))};
+}
+// ... and a refold restores slot cur; c0 .. c1: the changed raw positions, lb: the context before them
+__device__ __forceinline__ void inc_refold(IncM &inc, const KArgs &ka, int w, int g, int cur, int c0, int c1, int lb) {
+    const size_t Gf = inc_group_floats(ka.cells, ka.Nmax, 1);
+    const float *from = ka.tab + size_t(w) * 2 * ka.tab_slot + size_t(cur) * ka.tab_slot;
+    inc.src = reinterpret_cast<const u32 *>(from + size_t(g) * Gf);
+    inc.cc_src = reinterpret_cast<const uint4 *>(from + inc_cc_offset(ka.cells, ka.Nmax, ka.n_groups2, g));
+    inc.m_lo = c0 + 1 + lb;
+    inc.m_hi = c1 + 1 + lb;
+}
+
+// ---------------------------------------------------------------- setup and finish pieces
+// The motif sites' constraints: one wave per matching start o (mat[o] set by the
+// sequence scan), lanes = motif positions with partner table mpt
+template <class LT>
+__device__ __forceinline__ void motif_constraints(const LT &L, const int8_t *mpt, int mL, int N, int wid, int lane) {
+    for (int o = 1 + wid; o + mL - 1 <= N; o += NWV) {
+        if (!uni(L.mat[o])) continue;
+        bool ok = true;
+        for (int k = lane; k < mL; k += WAVE) {
+            const int pk = mpt[k];
+            if (pk < 0) ok = ok && L.up[o + k] >= 1;
+            else if (pk > k) ok = ok && allowed(L, o + k, o + pk);
+        }
+        const bool all = __ballot(!ok) == 0;
+        if (lane == 0) L.mat[o] = all ? 1 : 0;
+    }
+}
+// q5[0..4]: no pair fits (one thread)
+template <class LT>
+__device__ __forceinline__ void q5_start(const LT &L, int N) {
+    L.q5[0] = 0u;
+    for (int j = 1; j <= 4 && j <= N; j++) L.q5[j] = (L.up[j] >= 1) ? L.q5[j - 1] : INF16;
+}
+
+// After the sweep: the three tables, q5 and the codes to the slot the fold
+// writes (the next proposal's unchanged cells), and the exactness guard of the
+// 16-bit encoding, every stored value >= floor.  Returns this thread's part of
+// the guard; the caller ORs it over the workgroup
+template <int NT, class LT>
+__device__ __forceinline__ bool fold_writeback(const KArgs &ka, const LT &L, const IncM &inc, int N) {
+    const int tid = threadIdx.x;
+    if (inc.dst) {
+        const size_t C = size_t(ka.cells);
+        u32 *dp = inc.dst;
+        for (int k = tid; k < int(C); k += NT) {
+            dp[k] = L.qbm[k];
+            dp[C + k] = L.qm[k];
+            dp[2 * C + k] = L.qm1[k];
+        }
+        for (int k = tid; k <= N; k += NT) dp[3 * C + k] = L.q5[k];
+        const int C16 = (((N - 4) * (N - 3)) / 2 + 15) >> 4;
+        for (int k = tid; k < C16; k += NT) inc.cc_dst[k] = reinterpret_cast<const uint4 *>(L.cc)[k];
+    }
+    bool low = false;
+    const int C = ((N - 4) * (N - 3)) >> 1;
+    auto chk = [&](u32 x) { low |= mfe16_inexact(sv(x)); };
+    for (int k = tid; k < C; k += NT) {
+        chk(L.qbm[k]);
+        chk(L.qm[k]);
+        chk(L.qm1[k]);
+    }
+    for (int k = tid; k <= N; k += NT) chk(L.q5[k]);
+    return low;
+}
+
+// One thread: f5[N] = z of the group's two variants to gout (dcal/mol; a half of
+// 0x4000 and above = no structure); bad: a value left the exact range, so the
+// walker is re-folded by the FP32 MinPlus kernel and from scratch next time
+__device__ __forceinline__ void fold_result(const KArgs &ka, int w, const int *vs, float *gout, u32 z, bool bad) {
+    const s16x2 q = sv(z);
+    const int hv[2] = {q.x, q.y};
+    for (int h = 0; h < 2; h++) {
+        const double e = hv[h] >= 0x4000 ? double(INFINITY) : static_cast<double>(hv[h]) / 100.0;
+        gout[size_t(w) * ka.n_variants + vs[h]] = static_cast<float>(e);
+    }
+    if (bad && ka.ovf) {
+        ka.ovf[w] = 1;
+        if (ka.tab) ka.tab_valid[w] = 0;
+    }
+}
 
 }  // namespace
 }  // namespace adx

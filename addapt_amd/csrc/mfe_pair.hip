@@ -30,12 +30,17 @@
 // trips) are paid once per two diagonals.
 //
 // Every stored value goes through pfin() as in mfe_cells.hip.
+//
+// The file in reading order: the carve (CP, PLay), pair_setup (sequence, tables,
+// refold restore, per-cell pass; one copy for all waves), one function per role
+// (build_list / load_list, finalize on FRun, block_partials, split_rows,
+// q5_columns), mfe_pair_fold (the step loop, one instance per wave), the kernel
+// and its launcher.  mfe_common.hpp holds what mfe_cells.hip spells alike.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
-#include <type_traits>
 #include <utility>
 
 #include "dev_types.hpp"
@@ -47,11 +52,17 @@ namespace adx {
 
 #define PSTAMP(k) ADX_STAMP_AT(k)   // fold_common.hpp
 #ifdef ADX_STAMP
+// the roles that stamp inside take the sweep's counters
+#define PSTAMP_PARAMS , unsigned long long *st_acc, unsigned long long &st_last
+#define PSTAMP_ARGS , st_acc, st_last
 __device__ unsigned long long g_stamps_p[16][16];
 // the same sums as they stand after the early steps (span e0 = d - 2 has more than
 // 64 rows, so a fold from scratch finalizes in two lane-sets): the share of those
 // steps, which tells the wave that sets them
 __device__ unsigned long long g_stamps_pe[16][16];
+#else
+#define PSTAMP_PARAMS
+#define PSTAMP_ARGS
 #endif
 
 namespace {
@@ -60,22 +71,25 @@ namespace {
 // of qm (one span per wave), the lists and q5 ride on block waves, whose loop
 // sizes the generator partitions around them (tools/gen_mfe_blocks.py
 // PAIR_ROLES4; two workgroups per CU)
-#ifndef ADX_PAIR_NBLK
-#define ADX_PAIR_NBLK 7
-#endif
-// eight waves (ten waves with nine blocks measured -37 %: a 10-wave workgroup's
-// waves land 3, 3, 2, 2 on the SIMDs, so a second one does not fit at 96 VGPRs)
-constexpr int NWV = 8;
+// eight waves, NWV in mfe_common.hpp (ten waves with nine blocks measured
+// -37 %: a 10-wave workgroup's waves land 3, 3, 2, 2 on the SIMDs, so a second
+// one does not fit at 96 VGPRs)
+constexpr int PAIR_NBLK = 7;   // (a block on the finalize wave too, 8, measured -5.7 %: the finalize
+                               // wave then sets the step)
+constexpr int PRIO_ROLE = 2;   // s_setprio of the one-wave roles over the block waves
+// the waves of the one-wave roles
 constexpr int F_WAVE = 7;
-#ifndef ADX_PRIO_ROLE
-#define ADX_PRIO_ROLE 2
-#endif
-constexpr int PRIO_ROLE = ADX_PRIO_ROLE;   // s_setprio of the one-wave roles over the block waves
+constexpr int L_WAVE = 1;            // the lists two steps ahead (diagonals d+4, d+5) and their B records
+                                     // (round 5: wave 1 +0.8 % over wave 4, A/B r05zn/r05zo)
+constexpr int Q_WAVE = 3;            // q5 of two columns (on the finalize wave: -2.1 %, A/B r06n)
+constexpr int FW[2] = {F_WAVE, 6};   // finalize lane-sets 0, 1 (the first 64 rows, the rest): lane-set 1
+                                     // (a fold from scratch at spans < 38; a refold whose row window
+                                     // is longer, i.e. both partners of an enforced pair changed)
+                                     // rides on block wave 6
+constexpr int MW[2] = {0, 2};        // the split parts of spans d, d+1
 
-// (A/B round 6: a block on the finalize wave too, ADX_GEN_PAIR_NBLK=8, measured
-// -5.7 %: the finalize wave then sets the step; nine block waves in ten -37 %)
 #include "mfe_pair_blocks.inc"
-static_assert(MFE_NBLK == ADX_PAIR_NBLK, "one block per block wave");
+static_assert(MFE_NBLK == PAIR_NBLK, "one block per block wave");
 
 constexpr int PINF = 32767;   // an impossible half, sign-extended (the partial slots)
 
@@ -111,8 +125,6 @@ struct CP {
     int np;
 };
 
-constexpr size_t al16(size_t b) { return (b + 15) & ~size_t(15); }
-constexpr int MFE_E4_MAX = 64;
 template <int NM>
 struct PLay {
     static constexpr int NP = NM + 2;
@@ -148,15 +160,7 @@ struct PLay {
         l.ct = lds_at<u32>(CT);
         l.dt = lds_at<u32>(DT);
         l.cc = lds_at<uint8_t>(CC);
-        uint8_t *y = lds_at<uint8_t>(BY);
-        l.S = y;
-        l.up = y + NP;
-        l.dn = y + 2 * NP;
-        l.ptn = y + 3 * NP;
-        l.enc = y + 4 * NP;
-        l.flg = y + 5 * NP;
-        l.mat = y + 6 * NP;
-        l.raw = y + 7 * NP;
+        carve_bytes(l, lds_at<uint8_t>(BY), NP);
         l.cl = lds_at<uint8_t>(CLS);
         l.cnt = lds_at<int>(CNT);
         l.flag = lds_at<int>(FLAG);
@@ -169,21 +173,88 @@ struct PLay {
 };
 static_assert(MFE_E4_SLOTS <= MFE_E4_MAX, "CP::e4 holds the generated slots");
 
-struct IncM {
-    const u32 *src;
-    u32 *dst;
-    int m_lo, m_hi;
-    const uint4 *cc_src;   // the slots' per-cell codes (dev_types.hpp inc_cc_offset)
-    uint4 *cc_dst;
-};
-
-__device__ __forceinline__ int lanesets(int n) { return (n + 63) >> 6; }
 __device__ __forceinline__ int sext_lo(u32 x) { return int(short(x & 0xFFFFu)); }
 __device__ __forceinline__ int sext_hi(u32 x) { return int(x) >> 16; }
 __device__ __forceinline__ u32 pack2(int lo, int hi) { return (u32(lo) & 0xFFFFu) | (u32(hi) << 16); }
 
-// One instance per wave (WID): every wave's sweep holds only its own interior-loop
-// block and roles, so the registers of the other waves' roles are not live in it
+// The per-cell setup of quarter-sets 4 I0 .. 4 I0 + 15 (as in mfe_cells.hip):
+// inner-pair code, hairpin (+ motif) or the non-pairable mark, multiloop stem
+// of the pairable cells, for the changed band
+// (a fold from scratch: every cell; a refold restored the others).  Round 6:
+// the band's rows in quarter-sets of 16 (diagonal d, rows clo(d) + 16c ..), four
+// quarter-sets per 64-lane item and four items per batch, each batch in two LDS
+// round trips; items by diagonal left most lanes idle (a refold's band holds
+// d + 3 rows of diagonal d) and took three times the batches
+// qtab, tot: the quarter-set table; hpf: hairpin length factors; spk, spv: special hairpins
+__device__ __forceinline__ void cell_pass(const CP &L, const Band &bd, int lane, int I0, const u32 *qtab, int tot,
+                                          const u32 *hpf, const uint32_t *spk, const u32 *spv, int mL, u32 mextra) {
+    const int N = bd.N;
+    constexpr int NI = 4;   // items I0 .. I0 + 3 (quarter-sets 4 I .. 4 I + 3, lanes 16 g ..)
+    int ii[NI], jj[NI], dv[NI];
+    bool ok[NI];
+    u32 wim[NI], wi[NI], wi1[NI], wjm[NI], wj[NI], wjp[NI];
+    uint32_t mt[NI];
+#pragma unroll
+    for (int q = 0; q < NI; q++) {
+        const int k = 4 * (I0 + q) + (lane >> 4);   // the lane's quarter-set
+        const u32 e = qtab[k < tot ? k : 0];
+        const int d = k < tot ? int(e & 255) : 4;
+        const int r = int(e >> 8) + (lane & 15) - 1;
+        const bool v = k < tot && r < bd.chi(d);
+        dv[q] = d;
+        ok[q] = v;
+        const int i = ok[q] ? r + 1 : 1, j = ok[q] ? i + d : 5;
+        ii[q] = i;
+        jj[q] = j;
+        wim[q] = L.pos[i - 1];
+        wi[q] = L.pos[i];
+        wi1[q] = L.pos[i + 1];
+        wjm[q] = L.pos[j - 1];
+        wj[q] = L.pos[j];
+        wjp[q] = L.pos[j + 1];
+        mt[q] = L.mat[i];
+    }
+    int ty[NI], ix1[NI];
+    bool pr[NI], inb[NI];
+    u32 f1[NI], f2[NI], hv[NI];
+#pragma unroll
+    for (int q = 0; q < NI; q++) {
+        const int i = ii[q], j = jj[q], d = dv[q];
+        hv[q] = hpf[d - 1];
+        const int si = wi[q] & 7, sj = wj[q] & 7;
+        ty[q] = ptype(si, sj);
+        inb[q] = ok[q];
+        const int fi = (wi[q] >> 3) & 7, fj = (wj[q] >> 3) & 7;
+        const int pi = (wi[q] >> 16) & 255, pj = (wj[q] >> 16) & 255;
+        bool al = !((fi | fj) & 1) && !((fi & 2) || (fj & 4));
+        al = al && (pi ? pi == j : (pj ? pj == i : (wi[q] >> 24) == (wj[q] >> 24)));
+        pr[q] = inb[q] && ty[q] != 0 && al;
+        const int sim = wim[q] & 7, sjp = wjp[q] & 7, si1 = wi1[q] & 7, sjm = wjm[q] & 7;
+        ix1[q] = (d - 1 == 3) ? DT_TAU + ty[q] : DT_MMH + ty[q] * 25 + si1 * 5 + sjm;
+        f1[q] = L.dt[ix1[q]];
+        f2[q] = L.dt[DT_MLS + ty[q] * 25 + sim * 5 + sjp];
+    }
+#pragma unroll
+    for (int q = 0; q < NI; q++) {
+        const int i = ii[q], j = jj[q], d = dv[q], u = d - 1;
+        if (!ok[q]) continue;
+        L.cc[off(d, N) + i - 1] = static_cast<uint8_t>(rtype(ty[q]) * 25 + (wjp[q] & 7) * 5 + (wim[q] & 7));
+        u32 h = INF16;
+        if (((wi1[q] >> 8) & 255) >= uint32_t(u)) {
+            h = padd(hv[q], f1[q]);
+            if (u == 3 || u == 4 || u == 6) {   // special hairpins (three diagonals)
+                const int sh = special_hp(spk, hp_key(L.S, i, u + 2));
+                if (sh >= 0) h = spv[sh];
+            }
+        }
+        if (d == mL - 1 && mL > 0 && mt[q]) h = pmin(h, mextra);
+        if (inb[q]) {
+            L.qbm[off(d, N) + i - 1] = pr[q] ? h : MARK16;
+            L.qm1[colb(j) + i - 1] = pr[q] ? f2[q] : INF16;
+        }
+    }
+}
+
 // The fold's setup (sequence, tables, refold restore, per-cell pass) and its
 // write-back run in the kernel body, one copy of the code for all eight waves
 // (round 6: as part of the per-wave instances each wave fetched its own copy,
@@ -205,13 +276,9 @@ __device__ __forceinline__ bool pair_setup(const KArgs &ka, const DevScaled *__r
 #ifdef ADX_STAMP
     const unsigned long long st_setup0 = __builtin_amdgcn_s_memtime();
 #endif
-    const bool incr = inc.src != nullptr;
-    const int m_lo = uni(inc.m_lo), m_hi = uni(inc.m_hi);
-    // changed rows of span dd (cells containing a changed position; mfe_cells.hip)
-    auto clo = [&](int dd) { return incr ? max(1, m_lo - 1 - dd) : 1; };
-    auto chi = [&](int dd) { return incr ? min(N - dd, m_hi + 1) : N - dd; };
-    auto qlo = [&](int s) { return incr ? max(1, m_lo - 2 - s) : 1; };
-    auto qhi = [&](int s) { return incr ? min(N - s, m_hi + 2) : N - s; };
+    const Band bd = inc.band(N);
+    const bool incr = bd.incr;
+    const int m_lo = bd.m_lo;
 
     // ---- setup loads (round 6): every table element and sequence / constraint byte this
     // thread stores, all in flight at once and stored before the restore's loads are
@@ -369,17 +436,7 @@ __device__ __forceinline__ bool pair_setup(const KArgs &ka, const DevScaled *__r
             if (in) L.mat[o] = ok ? 1 : 0;
         }
         __syncthreads();
-        for (int o = 1 + wid; o + mL - 1 <= N; o += NT / WAVE) {
-            if (!uni(L.mat[o])) continue;
-            bool ok = true;
-            for (int k = lane; k < mL; k += WAVE) {
-                const int pk = mpt[k];
-                if (pk < 0) ok = ok && L.up[o + k] >= 1;
-                else if (pk > k) ok = ok && allowed(L, o + k, o + pk);
-            }
-            const bool all = __ballot(!ok) == 0;
-            if (lane == 0) L.mat[o] = all ? 1 : 0;
-        }
+        motif_constraints(L, mpt, mL, N, wid, lane);
     }
 #ifdef ADX_STAMP
     const unsigned long long st_s25 = __builtin_amdgcn_s_memtime();   // motif scan done
@@ -415,7 +472,7 @@ __device__ __forceinline__ bool pair_setup(const KArgs &ka, const DevScaled *__r
 #pragma unroll
     for (int xs = 0; xs < 2; xs++) {
         const int d = 4 + xs * WAVE + lane;
-        const int n = d <= N - 1 ? max(0, chi(d) - clo(d) + 1) : 0;
+        const int n = d <= N - 1 ? max(0, bd.chi(d) - bd.clo(d) + 1) : 0;
         const int q = (n + 15) >> 4;
         int v = q;
 #pragma unroll
@@ -424,94 +481,20 @@ __device__ __forceinline__ bool pair_setup(const KArgs &ka, const DevScaled *__r
             if (lane >= o) v += t;
         }
         if (wid == xs)
-            for (int c = 0; c < q; c++) qtab[tot + v - q + c] = u32(d) | (u32(clo(d) + 16 * c) << 8);
+            for (int c = 0; c < q; c++) qtab[tot + v - q + c] = u32(d) | (u32(bd.clo(d) + 16 * c) << 8);
         tot += __shfl(v, WAVE - 1, WAVE);
     }
     tot = uni(tot);
     __syncthreads();
     const u32 mx = __float_as_uint(XS->motif_extra);
     const u32 mextra = (mh0 ? (mx & 0xFFFFu) : 0x7FFFu) | (mh1 ? (mx & 0xFFFF0000u) : 0x7FFF0000u);
-    if (tid == 0) {
-        L.q5[0] = 0u;
-        for (int j = 1; j <= 4 && j <= N; j++) L.q5[j] = (L.up[j] >= 1) ? L.q5[j - 1] : INF16;
-    }
+    if (tid == 0) q5_start(L, N);
 #ifdef ADX_STAMP
     const unsigned long long st_s3 = __builtin_amdgcn_s_memtime();   // motif sites
 #endif
-    // ---- per-cell setup (mfe_cells.hip): inner-pair code, hairpin (+ motif) or the
-    // non-pairable mark, multiloop stem of the pairable cells, for the changed band
-    // (a fold from scratch: every cell; a refold restored the others).  Round 6:
-    // the band's rows in quarter-sets of 16 (diagonal d, rows clo(d) + 16c ..), four
-    // quarter-sets per 64-lane item and four items per batch, each batch in two LDS
-    // round trips; items by diagonal left most lanes idle (a refold's band holds
-    // d + 3 rows of diagonal d) and took three times the batches
-    auto cell_pass = [&](int I0) __attribute__((always_inline)) {
-        constexpr int NI = 4;   // items I0 .. I0 + 3 (quarter-sets 4 I .. 4 I + 3, lanes 16 g ..)
-        int ii[NI], jj[NI], dv[NI];
-        bool ok[NI];
-        u32 wim[NI], wi[NI], wi1[NI], wjm[NI], wj[NI], wjp[NI];
-        uint32_t mt[NI];
-#pragma unroll
-        for (int q = 0; q < NI; q++) {
-            const int k = 4 * (I0 + q) + (lane >> 4);   // the lane's quarter-set
-            const u32 e = qtab[k < tot ? k : 0];
-            const int d = k < tot ? int(e & 255) : 4;
-            const int r = int(e >> 8) + (lane & 15) - 1;
-            const bool v = k < tot && r < chi(d);
-            dv[q] = d;
-            ok[q] = v;
-            const int i = ok[q] ? r + 1 : 1, j = ok[q] ? i + d : 5;
-            ii[q] = i;
-            jj[q] = j;
-            wim[q] = L.pos[i - 1];
-            wi[q] = L.pos[i];
-            wi1[q] = L.pos[i + 1];
-            wjm[q] = L.pos[j - 1];
-            wj[q] = L.pos[j];
-            wjp[q] = L.pos[j + 1];
-            mt[q] = L.mat[i];
-        }
-        int ty[NI], ix1[NI];
-        bool pr[NI], inb[NI];
-        u32 f1[NI], f2[NI], hv[NI];
-#pragma unroll
-        for (int q = 0; q < NI; q++) {
-            const int i = ii[q], j = jj[q], d = dv[q];
-            hv[q] = hpf[d - 1];
-            const int si = wi[q] & 7, sj = wj[q] & 7;
-            ty[q] = ptype(si, sj);
-            inb[q] = ok[q];
-            const int fi = (wi[q] >> 3) & 7, fj = (wj[q] >> 3) & 7;
-            const int pi = (wi[q] >> 16) & 255, pj = (wj[q] >> 16) & 255;
-            bool al = !((fi | fj) & 1) && !((fi & 2) || (fj & 4));
-            al = al && (pi ? pi == j : (pj ? pj == i : (wi[q] >> 24) == (wj[q] >> 24)));
-            pr[q] = inb[q] && ty[q] != 0 && al;
-            const int sim = wim[q] & 7, sjp = wjp[q] & 7, si1 = wi1[q] & 7, sjm = wjm[q] & 7;
-            ix1[q] = (d - 1 == 3) ? DT_TAU + ty[q] : DT_MMH + ty[q] * 25 + si1 * 5 + sjm;
-            f1[q] = L.dt[ix1[q]];
-            f2[q] = L.dt[DT_MLS + ty[q] * 25 + sim * 5 + sjp];
-        }
-#pragma unroll
-        for (int q = 0; q < NI; q++) {
-            const int i = ii[q], j = jj[q], d = dv[q], u = d - 1;
-            if (!ok[q]) continue;
-            L.cc[off(d, N) + i - 1] = static_cast<uint8_t>(rtype(ty[q]) * 25 + (wjp[q] & 7) * 5 + (wim[q] & 7));
-            u32 h = INF16;
-            if (((wi1[q] >> 8) & 255) >= uint32_t(u)) {
-                h = padd(hv[q], f1[q]);
-                if (u == 3 || u == 4 || u == 6) {   // special hairpins (three diagonals)
-                    const int sh = special_hp(spk, hp_key(L.S, i, u + 2));
-                    if (sh >= 0) h = spv[sh];
-                }
-            }
-            if (d == mL - 1 && mL > 0 && mt[q]) h = pmin(h, mextra);
-            if (inb[q]) {
-                L.qbm[off(d, N) + i - 1] = pr[q] ? h : MARK16;
-                L.qm1[colb(j) + i - 1] = pr[q] ? f2[q] : INF16;
-            }
-        }
-    };
-    for (int I0 = wid * 4; 4 * I0 < tot; I0 += NWV * 4) cell_pass(I0);
+    // ---- per-cell setup of the changed band (cell_pass above)
+    for (int I0 = wid * 4; 4 * I0 < tot; I0 += NWV * 4)
+        cell_pass(L, bd, lane, I0, qtab, tot, hpf, spk, spv, mL, mextra);
 #ifdef ADX_STAMP
     const unsigned long long st_s35 = __builtin_amdgcn_s_memtime();   // this wave's cells (before the barrier)
 #endif
@@ -539,108 +522,601 @@ __device__ __forceinline__ bool pair_setup(const KArgs &ka, const DevScaled *__r
     return constrained;
 }
 
+// ---------------------------------------------------------------- the roles of a step
+// L: the pairable cells of diagonals db, db+1 (ranks < P0 on db) and the B records of
+// ranks < 64 into list slot sl (a step's B reads them two steps later: its first
+// lane-set's records are loaded a step ahead, across the barrier)
+__device__ __forceinline__ void build_list(const CP &L, const Band &bd, int lane, int db, int sl) {
+    const int N = bd.N, NP2 = 2 * L.np;
+    int base = 0, P0 = 0;
+    for (int k = 0; k < 2; k++) {
+        const int dn = db + k;
+        if (k == 1) P0 = base;
+        if (dn < 8 || dn > N - 1) continue;   // interior loops u >= 2 need spans >= 8
+        const int lo = bd.clo(dn), hi = bd.chi(dn);
+        const int Ln = lanesets(hi - lo + 1);
+        for (int ls = 0; ls < Ln; ls++) {
+            const int i = lo + ls * WAVE + lane;
+            const bool pr = i <= hi && L.qbm[off(dn, N) + i - 1] != MARK16;
+            const uint64_t m = __ballot(pr);
+            const int rk = base + __builtin_amdgcn_mbcnt_hi(uint32_t(m >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(m), 0u));
+            if (pr) L.cl[sl * NP2 + rk] = uint8_t(i);
+            if (pr && rk < WAVE) {
+                const int j = i + dn;
+                const int oc = brec_code(L, i, j);
+                const u32 mmo = L.dt[DT_MMI + oc];
+                u32 *rr = L.rec + sl * 2 * WAVE + rk;
+                rr[0] = brec_word(i, oc, L.up[i + 1], L.dn[j - 1]);
+                // one half of each energy: two-word records (mfe_cells.hip: three words)
+                rr[WAVE] = (mmo & 0xFFFFu) | (padd(L.ct[CT_ONEN + oc], mmo) << 16);
+            }
+            base += __popcll(m);
+        }
+    }
+    if (lane == 0) L.cnt[sl] = P0 | (base << 16);
+}
+// A step's list counts (CP::cnt) and its first lane-set's B record, loaded at the top
+// of the step before (issued with nothing to wait on: they complete under the
+// step's first read batch); the records of the 4-lanes-per-cell mapping (lane &
+// 15), the one of ~96 % of a refold's steps -- B reads its records itself when the
+// step maps its lanes otherwise
+__device__ __forceinline__ void load_list(const CP &L, int lane, int sl, int &PP, u32 &wd, u32 &mm) {
+    PP = L.cnt[sl];
+    const u32 *rr = L.rec + sl * 2 * WAVE + (lane & 15);
+    wd = rr[0];
+    mm = rr[WAVE];
+}
+
+// F's anchor and running values (the waves with a finalize lane-set)
+struct FRun {
+    int ab;                           // the anchor: lane 0 of lane-set 0 is row ab (0: not chosen yet)
+    int fd;                           // the step the values below stand for (0, or a step this wave sat out: none)
+    int oE0, oE1, oS1, oS2, oS3;      // uniform: off() of spans e0, e1, e0-1, e0-2, e0-3
+    uint32_t mS, mM;                  // uniform: split slots e0 % 6, (e0 + 4) % 6 (bytes)
+    uint32_t cW;                      // uniform: U slot e0 & 3 (bytes; the partials': twice that)
+    int fI;                           // per lane: the row,
+    uint32_t fSi, fSi1, fUi, fUi1;    //   S[i], S[i+1], up[i], up[i+1],
+    uint32_t fRq;                     //   the address of qm(i, i + 4) less 4 words,
+    uint32_t fJ4, fSj, fQ1;           //   4 jA, the addresses of S[jA - 1] and qm1(i, jA - 1)
+};
+
+// F: finalize e0 = d-2 and e1 = d-1 on lane-set fls.  mloF, mhiF: the changed hull (a
+// fold from scratch is a refold whose hull clamps nowhere).  Lanes = rows i, from
+// row fr to row lr.  A fold from scratch: all rows.  A refold: the rows whose
+// qm it rewrites (Band::qlo(e1) .. qhi(e0); the qbm / qm1 band lies inside) and one
+// ghost row m_hi + 3 above them, where the span has it.  The ghost writes no
+// table cell: it hands the restored qm of its two cells down as their unpaired
+// parts U.  That is exact: qm(r, j) = min(split(r, j), U(r, j)), and every split
+// of (r, j) plus the MLbase of the unpaired rows below r is a split of the row
+// that takes it (same right part, left part qm one row longer), so the band's
+// qm = min(split, U) is the same with either (tests/test_qm_boundary.py).
+// Rows above the ghost only carried U and are not run.  A lane-set spans 64
+// rows, consecutive lane-sets overlap by one row (lane 63 recomputes the next
+// set's first row for its U and writes nothing), so no value crosses waves;
+// the window's last row is row R (no cell of span e1) or the ghost, so the
+// last lane needs no neighbour.
+//
+// Lanes keep their rows: lane l of lane-set fls is row ab + 63 fls + l while
+// the anchor ab holds, and is masked off (EXEC) outside the step's window
+// [fr, lr].  The window only moves down (fr, lr never grow), so the anchor is
+// the lowest row from which the lane-sets still reach lr: max(1, lr - 63) for a
+// window of one lane-set, max(1, lr - 126) for a longer one, chosen at the first
+// step and again only when fr falls below it -- never in a fold from scratch
+// (fr = 1), at most once in a one-position refold (changed row >= 62).  Between
+// re-anchors every address is last step's plus a delta: the spans' cell offsets
+// and the ring slots are uniform shift registers, the lane's column and its qm1
+// column base advance by adds, its row's bytes and qm base stay
+// (tests/test_finalize_anchor_model.py restates all of it).
+template <int NM, int fls>
+__device__ __forceinline__ void finalize(const CP &L, FRun &f, const BUni &U, int N, int d, int lane, int mloF,
+                                         int mhiF, u32 mlclosing, u32 mlbase PSTAMP_PARAMS) {
+    static_assert(NM - 4 <= 2 * WAVE - 1, "two overlapping lane-sets reach every row from row 1");
+    static_assert(PLay<NM>::NP == NM + 2 && 4 * (NM + 2) * 4 < 65536, "slot strides as ds offsets");
+    const uint32_t aqm = lds_addr(L.qm), aqm1 = lds_addr(L.qm1);
+    const int e0 = d - 2, e1 = d - 1;
+    const int R = N - e0;                                   // rows of span e0 (e1: R - 1)
+    const int fr = max(1, mloF - 2 - e1);                   // Band::qlo(e1)
+    const int lr = min(R, mhiF + 3);
+    if (e0 <= N - 1 && (f.ab == 0 || fr < f.ab)) {              // (re-)anchor: both F waves alike
+        f.ab = max(1, lr - (lr - fr < 64 ? 63 : 126));
+        f.fd = 0;
+    }
+    if (e0 <= N - 1 && (fls == 0 || lr - f.ab > 63)) {        // lane-set 1: only past row ab + 63
+        __builtin_amdgcn_s_setprio(PRIO_ROLE);
+        constexpr uint32_t NP4 = uint32_t(NM + 2) * 4u;      // a ring slot, a partial half (bytes)
+        const uint32_t aq = U.aq, ac = U.ac, aS = lds_addr(L.S);
+        if (fls == 1 || f.fd != d) {   // the slow path: the closed forms at (ab, d); lane-set 1 (a block
+                                     // wave, a few steps of a wide refold) keeps no state but ab
+            f.fI = f.ab + fls * 63 + lane;
+            const int ic = min(f.fI, N);                       // rows past N are never active
+            f.fSi = L.S[ic], f.fSi1 = L.S[ic + 1], f.fUi = L.up[ic], f.fUi1 = L.up[ic + 1];
+            f.fRq = aqm + uint32_t(rowb(f.fI, N) - 4) * 4u;
+            const int jA = f.fI + e0;
+            f.fJ4 = uint32_t(jA) * 4u;
+            f.fSj = aS + uint32_t(jA - 1);
+            f.fQ1 = aqm1 + uint32_t(colb(jA - 1) + f.fI - 1) * 4u;
+            // inner cells of the stack / bulge-1 shapes: spans e0-1, e0-2, e0-3 (the
+            // impossible span 3 stands in for the ones no shape reads yet)
+            f.oE0 = off(e0, N), f.oE1 = off(e1, N);
+            f.oS1 = off(max(e0 - 1, 3), N), f.oS2 = off(max(e0 - 2, 3), N), f.oS3 = off(max(e0 - 3, 3), N);
+            f.mS = uint32_t(e0 % 6) * NP4, f.mM = uint32_t((e0 + 4) % 6) * NP4;
+            f.cW = uint32_t(e0 & 3) * NP4;
+            f.fd = d;
+        }
+        const int i = f.fI;
+        const uint32_t i4 = uint32_t(i) * 4u;
+        const uint32_t q1P = f.fQ1, q1A = q1P + (f.fJ4 - 20u), q1B = q1A + (f.fJ4 - 16u);   // colb(j+1) - colb(j) = j - 4
+        if (i >= fr && i <= lr) {
+        const bool own = lane < 63 || fls == 1 || lr - f.ab <= 63;   // the overlap lane writes nothing
+        const bool rowB = i <= R - 1;
+        const bool ghost = i == mhiF + 3;
+        const uint32_t qA = (aq + uint32_t(f.oE0 - 1) * 4u) + i4, qB = (aq + uint32_t(f.oE1 - 1) * 4u) + i4;
+        const uint32_t pA = (lds_addr(L.part) + 2u * f.cW) + i4;       // slot e0 & 3; e1 & 3 is the next
+        const uint32_t uW = (lds_addr(L.colmin) + f.cW) + f.fJ4;         // U(.., jA) of span e0; e1: the next slot
+        const uint32_t gq = f.fRq + uint32_t(e0) * 4u;                 // qm(i, jA), qm(i, jA + 1)
+        u32 initA, cceA, stA, pqA, mlA, spA, upA, a0, a1, vS3, cS3, vS3b, cS3b, vS2, cS2, vS2b, cS2b, vS1, cS1;
+        u32 initB, cceB, stB, mlB, spB, b0, b1, gqA, gqB;
+        uint32_t sjm, sj, sjp, ujA, ujB, djm, dj;
+        const uint32_t si = f.fSi, si1 = f.fSi1, ui = f.fUi, ui1 = f.fUi1;
+        {
+            const uint32_t mA = (lds_addr(L.mla) + f.mM + 4u) + i4;   // span e0-2 (slot (e0 + 4) % 6), row i + 1; e1-2: the next slot
+            const uint32_t sA = (lds_addr(L.mla) + f.mS) + i4;        // slot e0 % 6; e1 % 6 is the next
+            const uint32_t uA = (lds_addr(L.colmin) + 3u * NP4 - f.cW) + f.fJ4;   // span e0-1: slot (e0 + 3) & 3
+            asm volatile(
+                "ds_read_b32 %[initA], %[qA]\n"
+                "ds_read_u8 %[cceA], %[kA]\n"
+                "ds_read_b32 %[stA], %[q1A]\n"
+                "ds_read_b32 %[pqA], %[q1P]\n"
+                "ds_read_b32 %[mlA], %[mA]\n"
+                "ds_read_b32 %[spA], %[sA]\n"
+                "ds_read_b32 %[upA], %[uA]\n"
+                "ds_read_b32 %[a0], %[pA]\n"
+                "ds_read_b32 %[a1], %[pA] offset:%[pst]\n"
+                "ds_read_b32 %[initB], %[qB]\n"
+                "ds_read_u8 %[cceB], %[kB]\n"
+                "ds_read_b32 %[stB], %[q1B]\n"
+                "ds_read_b32 %[mlB], %[mA] offset:%[pst]\n"
+                "ds_read_b32 %[spB], %[sA] offset:%[pst]\n"
+                "ds_read_b32 %[b0], %[pA] offset:%[pst2]\n"
+                "ds_read_b32 %[b1], %[pA] offset:%[pst3]\n"
+                "ds_read_b32 %[vS3], %[q3]\n"
+                "ds_read_b32 %[vS3b], %[q3] offset:4\n"
+                "ds_read_b32 %[vS2], %[q2]\n"
+                "ds_read_b32 %[vS2b], %[q2] offset:4\n"
+                "ds_read_b32 %[vS1], %[q1]\n"
+                "ds_read_u8 %[cS3], %[k3]\n"
+                "ds_read_u8 %[cS3b], %[k3] offset:1\n"
+                "ds_read_u8 %[cS2], %[k2]\n"
+                "ds_read_u8 %[cS2b], %[k2] offset:1\n"
+                "ds_read_u8 %[cS1], %[k1]\n"
+                // S, up, dn lie NP bytes apart (the carve): one address, jA - 1 in S
+                "ds_read_u8 %[sjm], %[aSj] offset:0\n"
+                "ds_read_u8 %[sj], %[aSj] offset:1\n"
+                "ds_read_u8 %[sjp], %[aSj] offset:2\n"
+                "ds_read_u8 %[ujA], %[aSj] offset:%[ou0]\n"
+                "ds_read_u8 %[ujB], %[aSj] offset:%[ou1]\n"
+                "ds_read_u8 %[djm], %[aSj] offset:%[od0]\n"
+                "ds_read_u8 %[dj], %[aSj] offset:%[od1]\n"
+                "ds_read_b32 %[gqA], %[gq]\n"
+                "ds_read_b32 %[gqB], %[gq] offset:4\n"
+                "s_waitcnt lgkmcnt(0)"
+                : [initA] "=&v"(initA), [cceA] "=&v"(cceA), [stA] "=&v"(stA), [pqA] "=&v"(pqA), [mlA] "=&v"(mlA),
+                  [spA] "=&v"(spA), [upA] "=&v"(upA), [a0] "=&v"(a0), [a1] "=&v"(a1), [initB] "=&v"(initB),
+                  [cceB] "=&v"(cceB), [stB] "=&v"(stB), [mlB] "=&v"(mlB), [spB] "=&v"(spB), [b0] "=&v"(b0),
+                  [b1] "=&v"(b1), [vS3] "=&v"(vS3), [vS3b] "=&v"(vS3b), [vS2] "=&v"(vS2), [vS2b] "=&v"(vS2b),
+                  [vS1] "=&v"(vS1), [cS3] "=&v"(cS3), [cS3b] "=&v"(cS3b), [cS2] "=&v"(cS2), [cS2b] "=&v"(cS2b),
+                  [cS1] "=&v"(cS1), [sjm] "=&v"(sjm), [sj] "=&v"(sj), [sjp] "=&v"(sjp), [ujA] "=&v"(ujA),
+                  [ujB] "=&v"(ujB), [djm] "=&v"(djm), [dj] "=&v"(dj), [gqA] "=&v"(gqA), [gqB] "=&v"(gqB)
+                : [qA] "v"(qA), [kA] "v"((ac + uint32_t(f.oE0 - 1)) + uint32_t(i)), [q1A] "v"(q1A), [q1P] "v"(q1P),
+                  [mA] "v"(mA), [sA] "v"(sA), [uA] "v"(uA), [pA] "v"(pA), [pst] "i"(NP4), [pst2] "i"(2 * NP4),
+                  [pst3] "i"(3 * NP4), [qB] "v"(qB), [kB] "v"((ac + uint32_t(f.oE1 - 1)) + uint32_t(i)), [q1B] "v"(q1B),
+                  [q3] "v"((aq + uint32_t(f.oS3) * 4u) + i4), [q2] "v"((aq + uint32_t(f.oS2) * 4u) + i4),
+                  [q1] "v"((aq + uint32_t(f.oS1) * 4u) + i4), [k3] "v"((ac + uint32_t(f.oS3)) + uint32_t(i)),
+                  [k2] "v"((ac + uint32_t(f.oS2)) + uint32_t(i)), [k1] "v"((ac + uint32_t(f.oS1)) + uint32_t(i)),
+                  [aSj] "v"(f.fSj), [ou0] "i"(NM + 2 + 1), [ou1] "i"(NM + 2 + 2), [od0] "i"(2 * (NM + 2)),
+                  [od1] "i"(2 * (NM + 2) + 1), [gq] "v"(gq)
+                : "memory");
+        }
+#ifdef ADX_STAMP_F
+        PSTAMP(11);   // F: the read batch
+#endif
+        static_assert(NM + 2 == PLay<NM>::NP, "partial halves are NP words apart");
+        // the loop-correction factors of the stack / bulge-1 shapes and the cells' own terms
+        const int tyA = ptype(si, sj), tyB = ptype(si, sjp);
+        const int t8A = tyA * 8, t8B = tyB * 8;
+        auto stk = [&](u32 v, u32 c, int t8) {   // inner pair with code c closing a stack with type t8/8
+            return padd(v, padd(L.ct[CT_INVMM + c], L.ct[CT_STK + t8 + ((int(c) * 41) >> 10)]));
+        };
+        // A = (i, jA): stack inner (i+1, jA-1) span e0-2 [vS2]; bulges (0,1) inner
+        // (i+1, jA-2) [vS3], (1,0) inner (i+2, jA-1) [vS3b], span e0-3.
+        // B = (i, jA+1): stack inner (i+1, jA) span e0-1 [vS1]; bulges (0,1) inner
+        // (i+1, jA-1) [vS2], (1,0) inner (i+2, jA) [vS2b], span e0-2.
+        u32 iA = INF16, iB = INF16;
+        if (e0 >= 6) iA = stk(vS2, cS2, t8A);
+        if (e0 >= 7) {
+            iA = pmin(iA, djm >= 1 ? padd(stk(vS3, cS3, t8A), U.fs1) : INF16);
+            iA = pmin(iA, ui1 >= 1 ? padd(stk(vS3b, cS3b, t8A), U.fs1) : INF16);
+        }
+        if (e1 >= 6) iB = stk(vS1, cS1, t8B);
+        if (e1 >= 7) {
+            iB = pmin(iB, dj >= 1 ? padd(stk(vS2, cS2, t8B), U.fs1) : INF16);
+            iB = pmin(iB, ui1 >= 1 ? padd(stk(vS2b, cS2b, t8B), U.fs1) : INF16);
+        }
+        const u32 mlclA = padd(mlclosing, L.dt[DT_MLS + rtype(tyA) * 25 + sjm * 5 + si1]);
+        const u32 mlclB = padd(mlclosing, L.dt[DT_MLS + rtype(tyB) * 25 + sj * 5 + si1]);
+        const u32 mmiA = L.dt[DT_MMI + cceA], mmiB = L.dt[DT_MMI + cceB];
+        // the band's rows of the two spans (Band::clo .. chi; the window's rows have i <= R)
+        const bool inA = i >= mloF - 1 - e0 && i <= mhiF + 1;
+        const bool inB = rowB && e1 <= N - 1 && i >= mloF - 1 - e1 && i <= mhiF + 1;
+        auto st32 = [](uint32_t a, u32 v) { *lds_at<u32>(a) = v; };   // the batch's addresses serve the stores
+        // cell A
+        u32 m1A = stA;   // restored qm1 outside the band
+        if (inA) {
+            const u32 prev = (e0 >= 5 && ujA >= 1) ? padd(pqA, mlbase) : INF16;
+            u32 f1 = prev;
+            if (initA != MARK16) {
+                u32 c = pmin(initA, pack2(int(a0), int(a1)));
+                c = pmin(c, iA);
+                c = pfin(pmin(c, padd(mlA, mlclA)));
+                if (own) st32(qA, pfin(padd(c, mmiA)));
+                f1 = pmin(padd(c, stA), prev);
+            }
+            m1A = pfin(f1);
+            if (own) st32(q1A, m1A);
+        }
+        const u32 UA = ghost ? gqA : (ui >= 1 ? pmin(m1A, padd(upA, mlbase)) : m1A);
+        // cell B (its qm1 predecessor (i, jA) is cell A of this lane)
+        u32 m1B = stB;
+        if (inB) {
+            const u32 prev = (e1 >= 5 && ujB >= 1) ? padd(m1A, mlbase) : INF16;
+            u32 f1 = prev;
+            if (initB != MARK16) {
+                u32 c = pmin(initB, pack2(int(b0), int(b1)));
+                c = pmin(c, iB);
+                c = pfin(pmin(c, padd(mlB, mlclB)));
+                if (own) st32(qB, pfin(padd(c, mmiB)));
+                f1 = pmin(padd(c, stB), prev);
+            }
+            m1B = pfin(f1);
+            if (own) st32(q1B, m1B);
+        }
+#ifdef ADX_STAMP_F
+        PSTAMP(12);   // F: the cells' terms
+#endif
+        // U of row i+1 in column jA+1 (span e0) is the next lane's cell A (a window
+        // row below lr has its neighbour in the window: both lanes are on)
+        const u32 UA1 = u32(__builtin_amdgcn_ds_bpermute((lane + 1) * 4, int(UA)));
+        const u32 UB = ghost ? gqB : (ui >= 1 ? pmin(m1B, padd(UA1, mlbase)) : m1B);
+        if (own) {
+            st32(uW, UA);
+            st32(pA, u32(PINF));
+            st32(pA + NP4, u32(PINF));
+            if (e0 <= N - 3 && i >= mloF - 2 - e0 && i <= min(R, mhiF + 2))   // Band::qlo(e0) .. qhi(e0)
+                st32(gq, pfin(pmin(e0 >= 9 ? spA : INF16, UA)));
+        }
+        if (own && rowB && e1 <= N - 1) {
+            st32(uW + NP4 + 4u, UB);
+            st32(pA + 2u * NP4, u32(PINF));
+            st32(pA + 3u * NP4, u32(PINF));
+            if (e1 <= N - 3 && i >= mloF - 2 - e1 && i <= min(R - 1, mhiF + 2))   // Band::qlo(e1) .. qhi(e1)
+                st32(gq + 4u, pfin(pmin(e1 >= 9 ? spB : INF16, UB)));
+        }
+#ifdef ADX_STAMP_F
+        PSTAMP(13);   // F: U, the stores
+#endif
+        }
+#ifdef ADX_STAMP_F
+        {   // the sub-phase sums were advanced by the window's lanes only: every lane
+            // (lane 0 reports) takes them from the first lane of the window
+            const uint64_t on = __ballot(i >= fr && i <= lr);
+            if (on != 0) {
+                const int src = __ffsll((long long)on) - 1;
+                auto from = [&](unsigned long long v) {
+                    const uint32_t lo = __builtin_amdgcn_readlane(uint32_t(v), src);
+                    const uint32_t hi = __builtin_amdgcn_readlane(uint32_t(v >> 32), src);
+                    return (unsigned long long)lo | ((unsigned long long)hi << 32);
+                };
+                st_acc[11] = from(st_acc[11]), st_acc[12] = from(st_acc[12]), st_acc[13] = from(st_acc[13]);
+                st_last = from(st_last);
+            }
+        }
+#endif
+        // the running values of the next step
+        if constexpr (fls == 0) {
+        f.fQ1 = q1B;                       // qm1(i, jA + 1): the predecessor column of step d + 2
+        f.fJ4 += 8u, f.fSj += 2u;
+        f.oS3 = f.oS1, f.oS2 = f.oE0, f.oS1 = f.oE1;
+        f.oE0 = f.oE1 + (N - e1), f.oE1 = f.oE0 + (N - e1 - 1);   // off(e + 1) = off(e) + N - e
+        f.mM = f.mS, f.mS = f.mS == 4u * NP4 ? 0u : f.mS + 2u * NP4;
+        f.cW ^= 2u * NP4;
+        f.fd = d + 2;
+        }
+        __builtin_amdgcn_s_setprio(0);
+    }
+}
+
+// log2 slices (lanes) per cell of a lane-set over P cells
+__device__ __forceinline__ int slices(int P) { return P <= 16 ? 2 : (P <= 32 ? 1 : 0); }
+// the record's two energies, each 16 bits wide, to packed apo | holo words
+__device__ __forceinline__ u32 lo2(u32 x) { return __builtin_amdgcn_perm(x, x, 0x05040504u); }
+__device__ __forceinline__ u32 hi2(u32 x) { return __builtin_amdgcn_perm(x, x, 0x07060706u); }
+
+// B: interior-loop partials (u >= 2) of diagonals d and d+1.
+// Lanes = the pairable cells of both (listed last step: ranks < P0 on d,
+// the rest on d+1); a lane of d+1 reads its inner cells at
+// off(d - 2 - u) + i + (N - d + 2 + u), which the blocks add per lane (hb).
+// cPP, cwd, cmm: load_list of this step; blk: the wave's block
+template <int blk>
+__device__ __forceinline__ void block_partials(const CP &L, const DevTables &T, BUni &U, int d, int lane, int sl, int cPP,
+                                               u32 cwd, u32 cmm, bool constrained, u32 tauE, u32 fsm5 PSTAMP_PARAMS) {
+    const int N = U.N, NP = L.np, NP2 = 2 * NP;
+    const uint32_t ae4 = lds_addr(L.e4);
+    if (d + 1 >= 8 && d <= N - 1) {
+        const int P0 = uni(cPP & 0xFFFF), P = uni(cPP >> 16);
+        const int sh = slices(P);
+        const int cwl = 6 - sh;
+        const int Lb = (P + (1 << cwl) - 1) >> cwl;
+        const int r = lane >> cwl;
+        U.d = d;
+        U.umax = d - 5 < 30 ? d - 5 : 30;   // d+1's loop sizes; d's last one reads the impossible span 3
+        for (int ls = 0; ls < Lb && blk < MFE_NBLK; ls++) {
+            const int idx = (ls << cwl) + (lane & ((1 << cwl) - 1));
+            if (idx < P) {
+                const int hb = idx >= P0 ? 1 : 0;   // hb, dd: this kernel's two diagonals per lane-set
+                const int dd = d + hb;
+                BRec c;
+                if (ls == 0 && sh == 2) {   // loaded a step ahead
+                    c = brec_unpack(cwd, lo2(cmm), hi2(cmm));
+                } else if (idx < WAVE) {
+                    const u32 *rr = L.rec + sl * 2 * WAVE + idx;
+                    c = brec_unpack(rr[0], lo2(rr[WAVE]), hi2(rr[WAVE]));
+                } else {
+                    const int i = L.cl[sl * NP2 + idx];
+                    c = brec_of(L, i, i + dd);
+                }
+                const int i = c.i, oc = c.oc, type = (oc * 41) >> 10;
+                const int uml = dd - 6 < 30 ? dd - 6 : 30;   // this lane's loop sizes
+                BCell C;
+                C.i = i + hb * (N - d + 2);
+                C.hb = hb;
+                C.ty8 = type * 8;
+                bcell_slice(C, r, sh, ae4);
+                C.A = c.A;
+                C.B = c.B;
+                const u32 tau = type > 2 ? tauE : 0u;
+                // the loop sizes' table energies only on the wave whose block reads them
+                // (bits of a literal: a runtime-indexed table would be a scalar load;
+                // per block in mfe_cells.hip)
+                auto has = [&](unsigned bits) { return ((bits >> (sh * 8 + blk)) & 1u) != 0; };
+                C.m23f = has(size_bits(5)) ? padd(L.ct[CT_M23O + oc], fsm5) : INF16;
+                C.t11 = C.t12 = C.t21 = C.t22 = INF16;
+                bcell_tables(C, L, T, N, dd, i, oc, uml, has(size_bits(2)), has(size_bits(3)), has(size_bits(4)));
+                Acc a{INF16, INF16, INF16, INF16, INF16, INF16};
+                const bool mk = constrained && __ballot(C.A < uml || C.B < uml) != 0;
+                U.mk = mk;
+                PSTAMP(9);
+                if (sh == 2) mfe_block_s4(blk, U, C, a);
+                else if (sh == 1) mfe_block_s2(blk, U, C, a);
+                else mfe_block(blk, U, C, a);
+                PSTAMP(10);
+                const u32 acc = acc_fold(a, C, sh, c.mmo, c.mo, tau);
+                if (r == 0) {   // by row, the block waves' minima meet in atomics (mfe_cells.hip: a slot per block)
+                    int *pp = L.part + (dd & 3) * 2 * NP + i;
+                    atomicMin(pp, sext_lo(acc));
+                    atomicMin(pp + NP, sext_hi(acc));
+                }
+            }
+        }
+    }
+}
+
+// 2 NR reads of a split-point chunk from t0 on (NR = 16, 8, 4: the chunk shapes are
+// uniform) in one batch, folded into sp0 / sp1
+template <int NR>
+__device__ __forceinline__ void split_chunk(const CP &L, int N, int i, int j, int Tt, int t0, u32 &sp0, u32 &sp1) {
+    const uint32_t aqm = lds_addr(L.qm), aqm1 = lds_addr(L.qm1);
+    u32 av[NR], rv[NR];
+    const uint32_t pa = aqm1 + uint32_t(colb(j) + i - 1 + t0) * 4u;
+    const uint32_t pr = aqm + uint32_t(rowb(i, N) - 5 + t0) * 4u;
+    if constexpr (NR == 16) {
+        asm volatile(
+                "ds_read_b32 %0, %32 offset:0\n"
+                "ds_read_b32 %1, %32 offset:4\n"
+                "ds_read_b32 %2, %32 offset:8\n"
+                "ds_read_b32 %3, %32 offset:12\n"
+                "ds_read_b32 %4, %32 offset:16\n"
+                "ds_read_b32 %5, %32 offset:20\n"
+                "ds_read_b32 %6, %32 offset:24\n"
+                "ds_read_b32 %7, %32 offset:28\n"
+                "ds_read_b32 %8, %32 offset:32\n"
+                "ds_read_b32 %9, %32 offset:36\n"
+                "ds_read_b32 %10, %32 offset:40\n"
+                "ds_read_b32 %11, %32 offset:44\n"
+                "ds_read_b32 %12, %32 offset:48\n"
+                "ds_read_b32 %13, %32 offset:52\n"
+                "ds_read_b32 %14, %32 offset:56\n"
+                "ds_read_b32 %15, %32 offset:60\n"
+                "ds_read_b32 %16, %33 offset:0\n"
+                "ds_read_b32 %17, %33 offset:4\n"
+                "ds_read_b32 %18, %33 offset:8\n"
+                "ds_read_b32 %19, %33 offset:12\n"
+                "ds_read_b32 %20, %33 offset:16\n"
+                "ds_read_b32 %21, %33 offset:20\n"
+                "ds_read_b32 %22, %33 offset:24\n"
+                "ds_read_b32 %23, %33 offset:28\n"
+                "ds_read_b32 %24, %33 offset:32\n"
+                "ds_read_b32 %25, %33 offset:36\n"
+                "ds_read_b32 %26, %33 offset:40\n"
+                "ds_read_b32 %27, %33 offset:44\n"
+                "ds_read_b32 %28, %33 offset:48\n"
+                "ds_read_b32 %29, %33 offset:52\n"
+                "ds_read_b32 %30, %33 offset:56\n"
+                "ds_read_b32 %31, %33 offset:60\n"
+            "s_waitcnt lgkmcnt(0)"
+            : "=&v"(av[0]), "=&v"(av[1]), "=&v"(av[2]), "=&v"(av[3]), "=&v"(av[4]), "=&v"(av[5]), "=&v"(av[6]), "=&v"(av[7]), "=&v"(av[8]), "=&v"(av[9]), "=&v"(av[10]), "=&v"(av[11]), "=&v"(av[12]), "=&v"(av[13]), "=&v"(av[14]), "=&v"(av[15]), "=&v"(rv[0]), "=&v"(rv[1]), "=&v"(rv[2]), "=&v"(rv[3]), "=&v"(rv[4]), "=&v"(rv[5]), "=&v"(rv[6]), "=&v"(rv[7]), "=&v"(rv[8]), "=&v"(rv[9]), "=&v"(rv[10]), "=&v"(rv[11]), "=&v"(rv[12]), "=&v"(rv[13]), "=&v"(rv[14]), "=&v"(rv[15])
+            : "v"(pa), "v"(pr)
+            : "memory");
+    } else if constexpr (NR == 4) {
+        asm volatile(
+                "ds_read_b32 %0, %8 offset:0\n"
+                "ds_read_b32 %1, %8 offset:4\n"
+                "ds_read_b32 %2, %8 offset:8\n"
+                "ds_read_b32 %3, %8 offset:12\n"
+                "ds_read_b32 %4, %9 offset:0\n"
+                "ds_read_b32 %5, %9 offset:4\n"
+                "ds_read_b32 %6, %9 offset:8\n"
+                "ds_read_b32 %7, %9 offset:12\n"
+            "s_waitcnt lgkmcnt(0)"
+            : "=&v"(av[0]), "=&v"(av[1]), "=&v"(av[2]), "=&v"(av[3]), "=&v"(rv[0]), "=&v"(rv[1]), "=&v"(rv[2]), "=&v"(rv[3])
+            : "v"(pa), "v"(pr)
+            : "memory");
+    } else {
+        asm volatile(
+                "ds_read_b32 %0, %16 offset:0\n"
+                "ds_read_b32 %1, %16 offset:4\n"
+                "ds_read_b32 %2, %16 offset:8\n"
+                "ds_read_b32 %3, %16 offset:12\n"
+                "ds_read_b32 %4, %16 offset:16\n"
+                "ds_read_b32 %5, %16 offset:20\n"
+                "ds_read_b32 %6, %16 offset:24\n"
+                "ds_read_b32 %7, %16 offset:28\n"
+                "ds_read_b32 %8, %17 offset:0\n"
+                "ds_read_b32 %9, %17 offset:4\n"
+                "ds_read_b32 %10, %17 offset:8\n"
+                "ds_read_b32 %11, %17 offset:12\n"
+                "ds_read_b32 %12, %17 offset:16\n"
+                "ds_read_b32 %13, %17 offset:20\n"
+                "ds_read_b32 %14, %17 offset:24\n"
+                "ds_read_b32 %15, %17 offset:28\n"
+            "s_waitcnt lgkmcnt(0)"
+            : "=&v"(av[0]), "=&v"(av[1]), "=&v"(av[2]), "=&v"(av[3]), "=&v"(av[4]), "=&v"(av[5]), "=&v"(av[6]), "=&v"(av[7]), "=&v"(rv[0]), "=&v"(rv[1]), "=&v"(rv[2]), "=&v"(rv[3]), "=&v"(rv[4]), "=&v"(rv[5]), "=&v"(rv[6]), "=&v"(rv[7])
+            : "v"(pa), "v"(pr)
+            : "memory");
+    }
+    // reads past this slice's end belong to the next slice (a split point
+    // counted twice leaves the minimum unchanged): only the row end Tt masks
+    const int lim = Tt - t0;
+    if (__ballot(lim < NR - 1) == 0) {
+#pragma unroll
+        for (int k = 0; k < NR; k += 2) {
+            sp0 = pmin(sp0, padd(rv[k], av[k]));
+            sp1 = pmin(sp1, padd(rv[k + 1], av[k + 1]));
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < NR; k += 2) {
+            sp0 = pmin(sp0, padd(rv[k], k <= lim ? av[k] : INF16));
+            sp1 = pmin(sp1, padd(rv[k + 1], k + 1 <= lim ? av[k + 1] : INF16));
+        }
+    }
+}
+
+// M: the split part of qm for span s (lanes = cells x
+// slices of the split points, mfe_cells.hip): min over t >= 5 of
+// qm(i, i+t-1) + qm1(i+t, j), written to the span's slot for F
+__device__ __forceinline__ void split_rows(const CP &L, const Band &bd, int s, int lane) {
+    const int N = bd.N, NP = L.np;
+    if (s < 9 || s > N - 3) return;   // no split point below span 9
+    __builtin_amdgcn_s_setprio(PRIO_ROLE);
+    const int lo = bd.qlo(s), hi = bd.qhi(s);
+    const int Lm = lanesets(hi - lo + 1);
+    const int Tt = s - 4;
+    u32 *slot = L.mla + (s % 6) * NP;
+    for (int ls = 0; ls < Lm; ls++) {
+        const int nc = min(WAVE, hi - lo + 1 - ls * WAVE);
+        const int lc = nc <= 1 ? 0 : 32 - __clz(nc - 1);
+        const int cst = 1 << lc, lsl = 6 - lc;
+        const int c = lane & (cst - 1), rr = lane >> lc;
+        int i = lo + ls * WAVE + c;
+        const bool valid = c < nc;
+        if (!valid) i = hi;
+        const int j = i + s;
+        const int nb = Tt - 4;                                  // split points t = 5..Tt
+        const int bs = nb > 0 ? (nb + (1 << lsl) - 1) >> lsl : 0;
+        u32 sp0 = INF16, sp1 = INF16;
+        // split points in chunks of 16 and a last chunk of 16, 8 or 4 (bs is uniform;
+        // round 5: +0.7 %, reads past a slice's end cost as much as the ones in it)
+        int t0 = 5 + rr * bs;
+        for (int ch = 0; ch < (bs >> 4); ch++, t0 += 16) split_chunk<16>(L, N, i, j, Tt, t0, sp0, sp1);
+        const int rem = bs & 15;
+        if (rem > 8) split_chunk<16>(L, N, i, j, Tt, t0, sp0, sp1);
+        else if (rem > 4) split_chunk<8>(L, N, i, j, Tt, t0, sp0, sp1);
+        else if (rem > 0) split_chunk<4>(L, N, i, j, Tt, t0, sp0, sp1);
+        u32 split = pmin(sp0, sp1);
+        for (int k = cst; k < WAVE; k <<= 1) split = pmin(split, u32(__shfl_xor(int(split), k, WAVE)));
+        if (valid && rr == 0) slot[i] = pfin(split);
+    }
+    __builtin_amdgcn_s_setprio(0);
+}
+
+// Q: q5[j] for j = d-3, d-2 in one pass over k (qbm spans <= d-3 are final)
+__device__ __forceinline__ void q5_columns(const CP &L, const Band &bd, int d, int lane) {
+    const int N = bd.N, m_lo = bd.m_lo;
+    const bool incr = bd.incr;
+    const int j0 = d - 3, j1 = d - 2;
+    const bool w0 = j0 >= 5 && j0 <= N && (!incr || j0 >= m_lo - 1);
+    const bool w1 = j1 >= 5 && j1 <= N && (!incr || j1 >= m_lo - 1);
+    if (w0 || w1) {
+        __builtin_amdgcn_s_setprio(PRIO_ROLE);
+        // the last step of an odd N has j1 = N + 1 (w1 false): its chain reads
+        // column N instead, so no read leaves the tables (the result is unused)
+        const int j1r = j1 <= N ? j1 : N;
+        const int s0 = L.S[j0], s1 = L.S[j1r];
+        const int sp0 = (j0 < N) ? L.S[j0 + 1] : 5, sp1 = (j1r < N) ? L.S[j1r + 1] : 5;   // no dangle past N
+        u32 acc0 = INF16, acc1 = INF16;
+        for (int k0 = 1; k0 <= j1r - 4; k0 += WAVE) {
+            const int kk = k0 + lane;
+            const bool ok1 = kk <= j1r - 4, ok0 = kk <= j0 - 4;
+            const int k = ok1 ? kk : 1;
+            const int sk = L.S[k], skm = (k > 1) ? L.S[k - 1] : 5;
+            const u32 q5k = L.q5[k - 1];
+            const int ix1 = off(j1r - k, N) + k - 1;
+            const int ix0 = off(max(j0 - k, 4), N) + k - 1;
+            const u32 ex1 = L.dt[DT_EXT + ptype(sk, s1) * 36 + skm * 6 + sp1];
+            const u32 ex0 = L.dt[DT_EXT + ptype(sk, s0) * 36 + skm * 6 + sp0];
+            const u32 t1 = padd(padd(q5k, L.qbm[ix1]), padd(L.ct[CT_INVMM + L.cc[ix1]], ex1));
+            const u32 t0 = padd(padd(q5k, L.qbm[ix0]), padd(L.ct[CT_INVMM + L.cc[ix0]], ex0));
+            acc1 = pmin(acc1, ok1 ? t1 : INF16);
+            acc0 = pmin(acc0, ok0 ? t0 : INF16);
+        }
+        const u32 red0 = wave_min(acc0), red1 = wave_min(acc1);
+        if (lane == 0) {
+            u32 q0 = L.q5[j0];   // restored (refold) or initial when not recomputed
+            if (w0) {
+                q0 = pfin(pmin((L.up[j0] >= 1) ? L.q5[j0 - 1] : INF16, red0));
+                L.q5[j0] = q0;
+            }
+            if (w1) L.q5[j1] = pfin(pmin((L.up[j1] >= 1) ? q0 : INF16, red1));
+        }
+        __builtin_amdgcn_s_setprio(0);
+    }
+}
+
+// One instance per wave (WID): every wave's sweep holds only its own interior-loop
+// block and roles, so the registers of the other waves' roles are not live in it
 template <int NT, int NM, int WID>
 __device__ __forceinline__ void mfe_pair_fold(const KArgs &ka, const DevScaled *__restrict__ XS,
                                               const DevTables *__restrict__ TT, const int *vs, const CP &L,
                                               const IncM &inc, const bool constrained, const unsigned long long *sst) {
     const DevVariant V = ka.variants[vs[0]];
     const int N = uni(V.N);
-    const int tid = threadIdx.x;
-    const int lane = tid & (WAVE - 1);
+    const int lane = threadIdx.x & (WAVE - 1);
     constexpr int wid = WID;
-    const int NP = L.np;
+    constexpr int fls = FW[0] == wid ? 0 : (FW[1] == wid ? 1 : -1);   // this wave's finalize lane-set
     const u32 *gct = reinterpret_cast<const u32 *>(XS->ctab);
-    const bool incr = inc.src != nullptr;
-    const int m_lo = uni(inc.m_lo), m_hi = uni(inc.m_hi);
-    auto clo = [&](int dd) { return incr ? max(1, m_lo - 1 - dd) : 1; };
-    auto chi = [&](int dd) { return incr ? min(N - dd, m_hi + 1) : N - dd; };
-    auto qlo = [&](int s) { return incr ? max(1, m_lo - 2 - s) : 1; };
-    auto qhi = [&](int s) { return incr ? min(N - s, m_hi + 2) : N - s; };
+    const Band bd = inc.band(N);
     const u32 mlclosing = __float_as_uint(XS->mlclosing);
     const u32 mlbase = __float_as_uint(XS->mlbase_sig);
-    const DevTables &T = *TT;
-    const u32 *T11 = reinterpret_cast<const u32 *>(&T.int11[0][0][0][0]);
-    const u32 *T21 = reinterpret_cast<const u32 *>(&T.int21[0][0][0][0][0]);
-    const u32 *T22 = reinterpret_cast<const u32 *>(&T.int22[0][0][0][0][0][0]);
     const u32 tauE = gct[CT_FSM + 6];
     const u32 fsm5 = gct[CT_FSM + 5];
-    const u32 fs1 = gct[CT_FSM + 1];
-    BUni U;
-    U.qbm = L.qbm;
-    U.cc = L.cc;
-    U.ct = L.ct;
-    U.gct = gct;
-    U.kg = reinterpret_cast<const uint4 *>(XS->ku16);
-    U.aq = lds_addr(L.qbm);
-    U.ac = lds_addr(L.cc);
-    U.act = lds_addr(L.ct);
-    U.fs1 = fs1;
-    U.il = reinterpret_cast<const u32 *>(XS->il);
-    U.nin = reinterpret_cast<const u32 *>(XS->nin);
-    U.N = N;
-    const uint32_t aqm = lds_addr(L.qm), aqm1 = lds_addr(L.qm1), ae4 = lds_addr(L.e4);
-    constexpr int L_WAVE = 1;           // (round 5: wave 1 +0.8 % over wave 4, A/B r05zn/r05zo) the lists two steps ahead (diagonals d+4, d+5) and their B records
-    constexpr int Q_WAVE = 3;           // q5 of two columns (on the finalize wave: -2.1 %, A/B r06n)
-    constexpr int fw[2] = {F_WAVE, 6};  // finalize lane-sets 0, 1 (the first 64 rows, the rest): lane-set 1
-                                        // (a fold from scratch at spans < 38; a refold whose row window
-                                        // is longer, i.e. both partners of an enforced pair changed)
-                                        // rides on block wave 6
-    constexpr int mw[2] = {0, 2};       // the split parts of spans d, d+1
-    constexpr int fls = fw[0] == wid ? 0 : (fw[1] == wid ? 1 : -1);
-    const int NP2 = 2 * NP;
-    // the pairable cells of diagonals db, db+1 (ranks < P0 on db) and the B records of
-    // ranks < 64 into list slot sl (a step's B reads them two steps later: its first
-    // lane-set's records are loaded a step ahead, across the barrier)
-    auto build_list = [&](int db, int sl) {
-        int base = 0, P0 = 0;
-        for (int k = 0; k < 2; k++) {
-            const int dn = db + k;
-            if (k == 1) P0 = base;
-            if (dn < 8 || dn > N - 1) continue;   // interior loops u >= 2 need spans >= 8
-            const int lo = clo(dn), hi = chi(dn);
-            const int Ln = lanesets(hi - lo + 1);
-            for (int ls = 0; ls < Ln; ls++) {
-                const int i = lo + ls * WAVE + lane;
-                const bool pr = i <= hi && L.qbm[off(dn, N) + i - 1] != MARK16;
-                const uint64_t m = __ballot(pr);
-                const int rk = base + __builtin_amdgcn_mbcnt_hi(uint32_t(m >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(m), 0u));
-                if (pr) L.cl[sl * NP2 + rk] = uint8_t(i);
-                if (pr && rk < WAVE) {
-                    const int j = i + dn;
-                    const int oc = ptype(L.S[i], L.S[j]) * 25 + L.S[i + 1] * 5 + L.S[j - 1];
-                    const u32 mmo = L.dt[DT_MMI + oc];
-                    u32 *rr = L.rec + sl * 2 * WAVE + rk;
-                    rr[0] = uint32_t(i) | (uint32_t(oc) << 8) | (uint32_t(L.up[i + 1]) << 16) |
-                            (uint32_t(L.dn[j - 1]) << 24);
-                    rr[WAVE] = (mmo & 0xFFFFu) | (padd(L.ct[CT_ONEN + oc], mmo) << 16);
-                }
-                base += __popcll(m);
-            }
-        }
-        if (lane == 0) L.cnt[sl] = P0 | (base << 16);
-    };
+    BUni U = buni(L, XS, N);
     if (wid == L_WAVE) {   // steps 0 (no B work: d + 1 < 8) and 1
         if (lane == 0) L.cnt[0] = 0;
-        build_list(8, 1);
+        build_list(L, bd, lane, 8, 1);
     }
     __syncthreads();
-    // the first lane-set's B record of the next step, loaded a step ahead
-    auto slices = [](int P) { return P <= 16 ? 2 : (P <= 32 ? 1 : 0); };   // log2 slices per cell
-    int cPP = 0;                // this step's list counts (CP::cnt), loaded a step ahead,
-    u32 cwd = 0, cmm = 0;       // and its first lane-set's B record
-    // loaded at the top of the step before (issued with nothing to wait on: they
-    // complete under the step's first read batch); the records of the 4-lanes-
-    // per-cell mapping (lane & 15), the one of ~96 % of a refold's steps -- B
-    // reads its records itself when the step maps its lanes otherwise
-    auto load_list = [&](int sl, int &PP, u32 &wd, u32 &mm) {
-        PP = L.cnt[sl];
-        const u32 *rr = L.rec + sl * 2 * WAVE + (lane & 15);
-        wd = rr[0];
-        mm = rr[WAVE];
-    };
-    // the record's two energies, each 16 bits wide, to packed apo | holo words
-    auto lo2 = [](u32 x) { return __builtin_amdgcn_perm(x, x, 0x05040504u); };
-    auto hi2 = [](u32 x) { return __builtin_amdgcn_perm(x, x, 0x07060706u); };
+    int cPP = 0;                // this step's list counts and first B record (load_list)
+    u32 cwd = 0, cmm = 0;
 
 #ifdef ADX_STAMP
     unsigned long long st_acc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -654,24 +1130,11 @@ __device__ __forceinline__ void mfe_pair_fold(const KArgs &ka, const DevScaled *
     st_acc[7] = sst[4];
     st_acc[14] = sst[5];
     st_acc[15] = sst[6];
-#endif
-#ifdef ADX_STAMP
     st_acc[8] = sst[0] + (st_last - st_sw0);   // setup + the sweep's prelude
 #endif
-    // ---- F's anchor and running values (the waves with a finalize lane-set; role F
-    // below).  A fold from scratch is a refold whose hull clamps nowhere.
-    const int mloF = incr ? m_lo : -4096, mhiF = incr ? m_hi : 4096;
-    static_assert(NM - 4 <= 2 * WAVE - 1, "two overlapping lane-sets reach every row from row 1");
-    static_assert(PLay<NM>::NP == NM + 2 && 4 * (NM + 2) * 4 < 65536, "slot strides as ds offsets");
-    int ab = 0;   // the anchor: lane 0 of lane-set 0 is row ab (0: not chosen yet)
-    int fd = 0;   // the step the values below stand for (0, or a step this wave sat out: none)
-    int oE0 = 0, oE1 = 0, oS1 = 0, oS2 = 0, oS3 = 0;   // uniform: off() of spans e0, e1, e0-1, e0-2, e0-3
-    uint32_t mS = 0, mM = 0;                           // uniform: split slots e0 % 6, (e0 + 4) % 6 (bytes)
-    uint32_t cW = 0;                                   // uniform: U slot e0 & 3 (bytes; the partials': twice that)
-    int fI = 0;                                        // per lane: the row,
-    uint32_t fSi = 0, fSi1 = 0, fUi = 0, fUi1 = 0;     //   S[i], S[i+1], up[i], up[i+1],
-    uint32_t fRq = 0;                                  //   the address of qm(i, i + 4) less 4 words,
-    uint32_t fJ4 = 0, fSj = 0, fQ1 = 0;                //   4 jA, the addresses of S[jA - 1] and qm1(i, jA - 1)
+    // a fold from scratch is a refold whose hull clamps nowhere
+    const int mloF = bd.incr ? bd.m_lo : -4096, mhiF = bd.incr ? bd.m_hi : 4096;
+    FRun f{};
     // (the finalize wave holding PRIO_ROLE through its whole sweep instead of around F
     // measured -1.1 %: its loop top then takes issue slots from the block waves, which
     // set the step once F is this short; profiles/fanchor_ab.txt)
@@ -685,552 +1148,21 @@ __device__ __forceinline__ void mfe_pair_fold(const KArgs &ka, const DevScaled *
         PSTAMP(0);
         int nPP = 0;
         u32 nwd = 0, nmm = 0;
-        if (wid < MFE_NBLK) load_list(sl1, nPP, nwd, nmm);   // the next step's, built a step ago
-        // ---------------- L: the pairable cells of diagonals d+4, d+5 (B's lanes two
-        // steps on; their qbm marks are the setup's) and the records of ranks < 64
-        if (wid == L_WAVE) {
+        if (wid < MFE_NBLK) load_list(L, lane, sl1, nPP, nwd, nmm);   // the next step's, built a step ago
+        if (wid == L_WAVE) {   // L: diagonals d+4, d+5 (B's lanes two steps on; their qbm marks are the setup's)
             __builtin_amdgcn_s_setprio(PRIO_ROLE);
-            build_list(d + 4, sl2);
+            build_list(L, bd, lane, d + 4, sl2);
             __builtin_amdgcn_s_setprio(0);
         }
         PSTAMP(1);
-        // ---------------- F: finalize e0 = d-2 and e1 = d-1.  Lanes = rows i, from
-        // row fr to row lr.  A fold from scratch: all rows.  A refold: the rows whose
-        // qm it rewrites (qlo(e1) .. qhi(e0); the qbm / qm1 band lies inside) and one
-        // ghost row m_hi + 3 above them, where the span has it.  The ghost writes no
-        // table cell: it hands the restored qm of its two cells down as their unpaired
-        // parts U.  That is exact: qm(r, j) = min(split(r, j), U(r, j)), and every split
-        // of (r, j) plus the MLbase of the unpaired rows below r is a split of the row
-        // that takes it (same right part, left part qm one row longer), so the band's
-        // qm = min(split, U) is the same with either (tests/test_qm_boundary.py).
-        // Rows above the ghost only carried U and are not run.  A lane-set spans 64
-        // rows, consecutive lane-sets overlap by one row (lane 63 recomputes the next
-        // set's first row for its U and writes nothing), so no value crosses waves;
-        // the window's last row is row R (no cell of span e1) or the ghost, so the
-        // last lane needs no neighbour.
-        //
-        // Lanes keep their rows: lane l of lane-set fls is row ab + 63 fls + l while
-        // the anchor ab holds, and is masked off (EXEC) outside the step's window
-        // [fr, lr].  The window only moves down (fr, lr never grow), so the anchor is
-        // the lowest row from which the lane-sets still reach lr: max(1, lr - 63) for a
-        // window of one lane-set, max(1, lr - 126) for a longer one, chosen at the first
-        // step and again only when fr falls below it -- never in a fold from scratch
-        // (fr = 1), at most once in a one-position refold (changed row >= 62).  Between
-        // re-anchors every address is last step's plus a delta: the spans' cell offsets
-        // and the ring slots are uniform shift registers, the lane's column and its qm1
-        // column base advance by adds, its row's bytes and qm base stay
-        // (tests/test_finalize_anchor_model.py restates all of it).
-        if constexpr (fls >= 0) {
-            const int e0 = d - 2, e1 = d - 1;
-            const int R = N - e0;                                   // rows of span e0 (e1: R - 1)
-            const int fr = max(1, mloF - 2 - e1);                   // qlo(e1)
-            const int lr = min(R, mhiF + 3);
-            if (e0 <= N - 1 && (ab == 0 || fr < ab)) {              // (re-)anchor: both F waves alike
-                ab = max(1, lr - (lr - fr < 64 ? 63 : 126));
-                fd = 0;
-            }
-            if (e0 <= N - 1 && (fls == 0 || lr - ab > 63)) {        // lane-set 1: only past row ab + 63
-                __builtin_amdgcn_s_setprio(PRIO_ROLE);
-                constexpr uint32_t NP4 = uint32_t(NM + 2) * 4u;      // a ring slot, a partial half (bytes)
-                const uint32_t aq = U.aq, ac = U.ac, aS = lds_addr(L.S);
-                if (fls == 1 || fd != d) {   // the slow path: the closed forms at (ab, d); lane-set 1 (a block
-                                             // wave, a few steps of a wide refold) keeps no state but ab
-                    fI = ab + fls * 63 + lane;
-                    const int ic = min(fI, N);                       // rows past N are never active
-                    fSi = L.S[ic], fSi1 = L.S[ic + 1], fUi = L.up[ic], fUi1 = L.up[ic + 1];
-                    fRq = aqm + uint32_t(rowb(fI, N) - 4) * 4u;
-                    const int jA = fI + e0;
-                    fJ4 = uint32_t(jA) * 4u;
-                    fSj = aS + uint32_t(jA - 1);
-                    fQ1 = aqm1 + uint32_t(colb(jA - 1) + fI - 1) * 4u;
-                    // inner cells of the stack / bulge-1 shapes: spans e0-1, e0-2, e0-3 (the
-                    // impossible span 3 stands in for the ones no shape reads yet)
-                    oE0 = off(e0, N), oE1 = off(e1, N);
-                    oS1 = off(max(e0 - 1, 3), N), oS2 = off(max(e0 - 2, 3), N), oS3 = off(max(e0 - 3, 3), N);
-                    mS = uint32_t(e0 % 6) * NP4, mM = uint32_t((e0 + 4) % 6) * NP4;
-                    cW = uint32_t(e0 & 3) * NP4;
-                    fd = d;
-                }
-                const int i = fI;
-                const uint32_t i4 = uint32_t(i) * 4u;
-                const uint32_t q1P = fQ1, q1A = q1P + (fJ4 - 20u), q1B = q1A + (fJ4 - 16u);   // colb(j+1) - colb(j) = j - 4
-                if (i >= fr && i <= lr) {
-                const bool own = lane < 63 || fls == 1 || lr - ab <= 63;   // the overlap lane writes nothing
-                const bool rowB = i <= R - 1;
-                const bool ghost = i == mhiF + 3;
-                const uint32_t qA = (aq + uint32_t(oE0 - 1) * 4u) + i4, qB = (aq + uint32_t(oE1 - 1) * 4u) + i4;
-                const uint32_t pA = (lds_addr(L.part) + 2u * cW) + i4;       // slot e0 & 3; e1 & 3 is the next
-                const uint32_t uW = (lds_addr(L.colmin) + cW) + fJ4;         // U(.., jA) of span e0; e1: the next slot
-                const uint32_t gq = fRq + uint32_t(e0) * 4u;                 // qm(i, jA), qm(i, jA + 1)
-                u32 initA, cceA, stA, pqA, mlA, spA, upA, a0, a1, vS3, cS3, vS3b, cS3b, vS2, cS2, vS2b, cS2b, vS1, cS1;
-                u32 initB, cceB, stB, mlB, spB, b0, b1, gqA, gqB;
-                uint32_t sjm, sj, sjp, ujA, ujB, djm, dj;
-                const uint32_t si = fSi, si1 = fSi1, ui = fUi, ui1 = fUi1;
-                {
-                    const uint32_t mA = (lds_addr(L.mla) + mM + 4u) + i4;   // span e0-2 (slot (e0 + 4) % 6), row i + 1; e1-2: the next slot
-                    const uint32_t sA = (lds_addr(L.mla) + mS) + i4;        // slot e0 % 6; e1 % 6 is the next
-                    const uint32_t uA = (lds_addr(L.colmin) + 3u * NP4 - cW) + fJ4;   // span e0-1: slot (e0 + 3) & 3
-                    asm volatile(
-                        "ds_read_b32 %[initA], %[qA]\n"
-                        "ds_read_u8 %[cceA], %[kA]\n"
-                        "ds_read_b32 %[stA], %[q1A]\n"
-                        "ds_read_b32 %[pqA], %[q1P]\n"
-                        "ds_read_b32 %[mlA], %[mA]\n"
-                        "ds_read_b32 %[spA], %[sA]\n"
-                        "ds_read_b32 %[upA], %[uA]\n"
-                        "ds_read_b32 %[a0], %[pA]\n"
-                        "ds_read_b32 %[a1], %[pA] offset:%[pst]\n"
-                        "ds_read_b32 %[initB], %[qB]\n"
-                        "ds_read_u8 %[cceB], %[kB]\n"
-                        "ds_read_b32 %[stB], %[q1B]\n"
-                        "ds_read_b32 %[mlB], %[mA] offset:%[pst]\n"
-                        "ds_read_b32 %[spB], %[sA] offset:%[pst]\n"
-                        "ds_read_b32 %[b0], %[pA] offset:%[pst2]\n"
-                        "ds_read_b32 %[b1], %[pA] offset:%[pst3]\n"
-                        "ds_read_b32 %[vS3], %[q3]\n"
-                        "ds_read_b32 %[vS3b], %[q3] offset:4\n"
-                        "ds_read_b32 %[vS2], %[q2]\n"
-                        "ds_read_b32 %[vS2b], %[q2] offset:4\n"
-                        "ds_read_b32 %[vS1], %[q1]\n"
-                        "ds_read_u8 %[cS3], %[k3]\n"
-                        "ds_read_u8 %[cS3b], %[k3] offset:1\n"
-                        "ds_read_u8 %[cS2], %[k2]\n"
-                        "ds_read_u8 %[cS2b], %[k2] offset:1\n"
-                        "ds_read_u8 %[cS1], %[k1]\n"
-                        // S, up, dn lie NP bytes apart (the carve): one address, jA - 1 in S
-                        "ds_read_u8 %[sjm], %[aSj] offset:0\n"
-                        "ds_read_u8 %[sj], %[aSj] offset:1\n"
-                        "ds_read_u8 %[sjp], %[aSj] offset:2\n"
-                        "ds_read_u8 %[ujA], %[aSj] offset:%[ou0]\n"
-                        "ds_read_u8 %[ujB], %[aSj] offset:%[ou1]\n"
-                        "ds_read_u8 %[djm], %[aSj] offset:%[od0]\n"
-                        "ds_read_u8 %[dj], %[aSj] offset:%[od1]\n"
-                        "ds_read_b32 %[gqA], %[gq]\n"
-                        "ds_read_b32 %[gqB], %[gq] offset:4\n"
-                        "s_waitcnt lgkmcnt(0)"
-                        : [initA] "=&v"(initA), [cceA] "=&v"(cceA), [stA] "=&v"(stA), [pqA] "=&v"(pqA), [mlA] "=&v"(mlA),
-                          [spA] "=&v"(spA), [upA] "=&v"(upA), [a0] "=&v"(a0), [a1] "=&v"(a1), [initB] "=&v"(initB),
-                          [cceB] "=&v"(cceB), [stB] "=&v"(stB), [mlB] "=&v"(mlB), [spB] "=&v"(spB), [b0] "=&v"(b0),
-                          [b1] "=&v"(b1), [vS3] "=&v"(vS3), [vS3b] "=&v"(vS3b), [vS2] "=&v"(vS2), [vS2b] "=&v"(vS2b),
-                          [vS1] "=&v"(vS1), [cS3] "=&v"(cS3), [cS3b] "=&v"(cS3b), [cS2] "=&v"(cS2), [cS2b] "=&v"(cS2b),
-                          [cS1] "=&v"(cS1), [sjm] "=&v"(sjm), [sj] "=&v"(sj), [sjp] "=&v"(sjp), [ujA] "=&v"(ujA),
-                          [ujB] "=&v"(ujB), [djm] "=&v"(djm), [dj] "=&v"(dj), [gqA] "=&v"(gqA), [gqB] "=&v"(gqB)
-                        : [qA] "v"(qA), [kA] "v"((ac + uint32_t(oE0 - 1)) + uint32_t(i)), [q1A] "v"(q1A), [q1P] "v"(q1P),
-                          [mA] "v"(mA), [sA] "v"(sA), [uA] "v"(uA), [pA] "v"(pA), [pst] "i"(NP4), [pst2] "i"(2 * NP4),
-                          [pst3] "i"(3 * NP4), [qB] "v"(qB), [kB] "v"((ac + uint32_t(oE1 - 1)) + uint32_t(i)), [q1B] "v"(q1B),
-                          [q3] "v"((aq + uint32_t(oS3) * 4u) + i4), [q2] "v"((aq + uint32_t(oS2) * 4u) + i4),
-                          [q1] "v"((aq + uint32_t(oS1) * 4u) + i4), [k3] "v"((ac + uint32_t(oS3)) + uint32_t(i)),
-                          [k2] "v"((ac + uint32_t(oS2)) + uint32_t(i)), [k1] "v"((ac + uint32_t(oS1)) + uint32_t(i)),
-                          [aSj] "v"(fSj), [ou0] "i"(NM + 2 + 1), [ou1] "i"(NM + 2 + 2), [od0] "i"(2 * (NM + 2)),
-                          [od1] "i"(2 * (NM + 2) + 1), [gq] "v"(gq)
-                        : "memory");
-                }
-#ifdef ADX_STAMP_F
-                PSTAMP(11);   // F: the read batch
-#endif
-                static_assert(NM + 2 == PLay<NM>::NP, "partial halves are NP words apart");
-                // the loop-correction factors of the stack / bulge-1 shapes and the cells' own terms
-                const int tyA = ptype(si, sj), tyB = ptype(si, sjp);
-                const int t8A = tyA * 8, t8B = tyB * 8;
-                auto stk = [&](u32 v, u32 c, int t8) {   // inner pair with code c closing a stack with type t8/8
-                    return padd(v, padd(L.ct[CT_INVMM + c], L.ct[CT_STK + t8 + ((int(c) * 41) >> 10)]));
-                };
-                // A = (i, jA): stack inner (i+1, jA-1) span e0-2 [vS2]; bulges (0,1) inner
-                // (i+1, jA-2) [vS3], (1,0) inner (i+2, jA-1) [vS3b], span e0-3.
-                // B = (i, jA+1): stack inner (i+1, jA) span e0-1 [vS1]; bulges (0,1) inner
-                // (i+1, jA-1) [vS2], (1,0) inner (i+2, jA) [vS2b], span e0-2.
-                u32 iA = INF16, iB = INF16;
-                if (e0 >= 6) iA = stk(vS2, cS2, t8A);
-                if (e0 >= 7) {
-                    iA = pmin(iA, djm >= 1 ? padd(stk(vS3, cS3, t8A), fs1) : INF16);
-                    iA = pmin(iA, ui1 >= 1 ? padd(stk(vS3b, cS3b, t8A), fs1) : INF16);
-                }
-                if (e1 >= 6) iB = stk(vS1, cS1, t8B);
-                if (e1 >= 7) {
-                    iB = pmin(iB, dj >= 1 ? padd(stk(vS2, cS2, t8B), fs1) : INF16);
-                    iB = pmin(iB, ui1 >= 1 ? padd(stk(vS2b, cS2b, t8B), fs1) : INF16);
-                }
-                const u32 mlclA = padd(mlclosing, L.dt[DT_MLS + rtype(tyA) * 25 + sjm * 5 + si1]);
-                const u32 mlclB = padd(mlclosing, L.dt[DT_MLS + rtype(tyB) * 25 + sj * 5 + si1]);
-                const u32 mmiA = L.dt[DT_MMI + cceA], mmiB = L.dt[DT_MMI + cceB];
-                // the band's rows of the two spans (clo .. chi; the window's rows have i <= R)
-                const bool inA = i >= mloF - 1 - e0 && i <= mhiF + 1;
-                const bool inB = rowB && e1 <= N - 1 && i >= mloF - 1 - e1 && i <= mhiF + 1;
-                auto st32 = [](uint32_t a, u32 v) { *lds_at<u32>(a) = v; };   // the batch's addresses serve the stores
-                // cell A
-                u32 m1A = stA;   // restored qm1 outside the band
-                if (inA) {
-                    const u32 prev = (e0 >= 5 && ujA >= 1) ? padd(pqA, mlbase) : INF16;
-                    u32 f1 = prev;
-                    if (initA != MARK16) {
-                        u32 c = pmin(initA, pack2(int(a0), int(a1)));
-                        c = pmin(c, iA);
-                        c = pfin(pmin(c, padd(mlA, mlclA)));
-                        if (own) st32(qA, pfin(padd(c, mmiA)));
-                        f1 = pmin(padd(c, stA), prev);
-                    }
-                    m1A = pfin(f1);
-                    if (own) st32(q1A, m1A);
-                }
-                const u32 UA = ghost ? gqA : (ui >= 1 ? pmin(m1A, padd(upA, mlbase)) : m1A);
-                // cell B (its qm1 predecessor (i, jA) is cell A of this lane)
-                u32 m1B = stB;
-                if (inB) {
-                    const u32 prev = (e1 >= 5 && ujB >= 1) ? padd(m1A, mlbase) : INF16;
-                    u32 f1 = prev;
-                    if (initB != MARK16) {
-                        u32 c = pmin(initB, pack2(int(b0), int(b1)));
-                        c = pmin(c, iB);
-                        c = pfin(pmin(c, padd(mlB, mlclB)));
-                        if (own) st32(qB, pfin(padd(c, mmiB)));
-                        f1 = pmin(padd(c, stB), prev);
-                    }
-                    m1B = pfin(f1);
-                    if (own) st32(q1B, m1B);
-                }
-#ifdef ADX_STAMP_F
-                PSTAMP(12);   // F: the cells' terms
-#endif
-                // U of row i+1 in column jA+1 (span e0) is the next lane's cell A (a window
-                // row below lr has its neighbour in the window: both lanes are on)
-                const u32 UA1 = u32(__builtin_amdgcn_ds_bpermute((lane + 1) * 4, int(UA)));
-                const u32 UB = ghost ? gqB : (ui >= 1 ? pmin(m1B, padd(UA1, mlbase)) : m1B);
-                if (own) {
-                    st32(uW, UA);
-                    st32(pA, u32(PINF));
-                    st32(pA + NP4, u32(PINF));
-                    if (e0 <= N - 3 && i >= mloF - 2 - e0 && i <= min(R, mhiF + 2))   // qlo(e0) .. qhi(e0)
-                        st32(gq, pfin(pmin(e0 >= 9 ? spA : INF16, UA)));
-                }
-                if (own && rowB && e1 <= N - 1) {
-                    st32(uW + NP4 + 4u, UB);
-                    st32(pA + 2u * NP4, u32(PINF));
-                    st32(pA + 3u * NP4, u32(PINF));
-                    if (e1 <= N - 3 && i >= mloF - 2 - e1 && i <= min(R - 1, mhiF + 2))   // qlo(e1) .. qhi(e1)
-                        st32(gq + 4u, pfin(pmin(e1 >= 9 ? spB : INF16, UB)));
-                }
-#ifdef ADX_STAMP_F
-                PSTAMP(13);   // F: U, the stores
-#endif
-                }
-#ifdef ADX_STAMP_F
-                {   // the sub-phase sums were advanced by the window's lanes only: every lane
-                    // (lane 0 reports) takes them from the first lane of the window
-                    const uint64_t on = __ballot(i >= fr && i <= lr);
-                    if (on != 0) {
-                        const int src = __ffsll((long long)on) - 1;
-                        auto from = [&](unsigned long long v) {
-                            const uint32_t lo = __builtin_amdgcn_readlane(uint32_t(v), src);
-                            const uint32_t hi = __builtin_amdgcn_readlane(uint32_t(v >> 32), src);
-                            return (unsigned long long)lo | ((unsigned long long)hi << 32);
-                        };
-                        st_acc[11] = from(st_acc[11]), st_acc[12] = from(st_acc[12]), st_acc[13] = from(st_acc[13]);
-                        st_last = from(st_last);
-                    }
-                }
-#endif
-                // the running values of the next step
-                if constexpr (fls == 0) {
-                fQ1 = q1B;                       // qm1(i, jA + 1): the predecessor column of step d + 2
-                fJ4 += 8u, fSj += 2u;
-                oS3 = oS1, oS2 = oE0, oS1 = oE1;
-                oE0 = oE1 + (N - e1), oE1 = oE0 + (N - e1 - 1);   // off(e + 1) = off(e) + N - e
-                mM = mS, mS = mS == 4u * NP4 ? 0u : mS + 2u * NP4;
-                cW ^= 2u * NP4;
-                fd = d + 2;
-                }
-                __builtin_amdgcn_s_setprio(0);
-            }
-        }
+        if constexpr (fls >= 0) finalize<NM, fls>(L, f, U, N, d, lane, mloF, mhiF, mlclosing, mlbase PSTAMP_ARGS);
         PSTAMP(2);
-        // ---------------- B: interior-loop partials (u >= 2) of diagonals d and d+1.
-        // Lanes = the pairable cells of both (listed last step: ranks < P0 on d,
-        // the rest on d+1); a lane of d+1 reads its inner cells at
-        // off(d - 2 - u) + i + (N - d + 2 + u), which the blocks add per lane (hb).
-        if (d + 1 >= 8 && d <= N - 1) {
-            const int P0 = uni(cPP & 0xFFFF), P = uni(cPP >> 16);
-            const int sh = slices(P);
-            const int cwl = 6 - sh;
-            const int Lb = (P + (1 << cwl) - 1) >> cwl;
-            constexpr int blk = wid;
-            const int r = lane >> cwl;
-            U.d = d;
-            U.umax = d - 5 < 30 ? d - 5 : 30;   // d+1's loop sizes; d's last one reads the impossible span 3
-            for (int ls = 0; ls < Lb && blk < MFE_NBLK; ls++) {
-                const int idx = (ls << cwl) + (lane & ((1 << cwl) - 1));
-                if (idx < P) {
-                    const int hb = idx >= P0 ? 1 : 0;
-                    const int dd = d + hb;
-                    int i, oc, cA, cB;
-                    u32 mmo, mo;
-                    if (ls == 0 && sh == 2) {   // loaded a step ahead
-                        const u32 wd = cwd;
-                        mmo = lo2(cmm);
-                        mo = hi2(cmm);
-                        i = wd & 255;
-                        oc = (wd >> 8) & 255;
-                        cA = (wd >> 16) & 255;
-                        cB = wd >> 24;
-                    } else if (idx < WAVE) {
-                        const u32 *rr = L.rec + sl * 2 * WAVE + idx;
-                        const u32 wd = rr[0];
-                        mmo = lo2(rr[WAVE]);
-                        mo = hi2(rr[WAVE]);
-                        i = wd & 255;
-                        oc = (wd >> 8) & 255;
-                        cA = (wd >> 16) & 255;
-                        cB = wd >> 24;
-                    } else {
-                        i = L.cl[sl * NP2 + idx];
-                        oc = ptype(L.S[i], L.S[i + dd]) * 25 + L.S[i + 1] * 5 + L.S[i + dd - 1];
-                        cA = L.up[i + 1];
-                        cB = L.dn[i + dd - 1];
-                        mmo = L.dt[DT_MMI + oc];
-                        mo = padd(L.ct[CT_ONEN + oc], mmo);
-                    }
-                    const int type = (oc * 41) >> 10;
-                    const int si1 = (oc / 5) % 5;
-                    const int sj1 = oc % 5;
-                    const int uml = dd - 6 < 30 ? dd - 6 : 30;   // this lane's loop sizes
-                    BCell C;
-                    C.i = i + hb * (N - d + 2);
-                    C.hb = hb;
-                    C.ty8 = type * 8;
-                    C.rs = uint32_t(r) * 4u;
-                    C.ee = ae4 + uint32_t(r) * 4u;
-                    C.r1 = (r & 1) != 0;
-                    C.r2 = (r & 2) != 0;
-                    C.eb = r & 1;
-                    C.ea = sh == 2 ? ((r & 1) ? -(r >> 1) : (r >> 1)) : ((r & 1) ? -1 : 1);
-                    C.ctb = (r & 2) ? CT_ONEN : CT_BUL;
-                    C.A = cA;
-                    C.B = cB;
-                    const u32 tau = type > 2 ? tauE : 0u;
-                    // the loop sizes' table energies only on the wave whose block reads them
-                    // (bits of a literal: a runtime-indexed table would be a scalar load)
-                    auto has = [&](unsigned bits) { return ((bits >> (sh * 8 + blk)) & 1u) != 0; };
-                    C.m23f = has(size_bits(5)) ? padd(L.ct[CT_M23O + oc], fsm5) : INF16;
-                    C.t11 = C.t12 = C.t21 = C.t22 = INF16;
-                    {   // 1x1..2x2 energies from HBM (L2), used at the block end
-                        const int ty8 = type * 8;
-                        if (has(size_bits(2)) && uml >= 2) {
-                            const int c2 = L.cc[off(dd - 4, N) + i + 1];
-                            C.t11 = T11[((ty8 + ((c2 * 41) >> 10)) * 5 + si1) * 5 + sj1];
-                        }
-                        if (has(size_bits(3)) && uml >= 3) {
-                            const int o3 = off(dd - 5, N) + i;
-                            const int a2 = L.cc[o3 + 1], b2 = L.cc[o3 + 2];
-                            const int ta = (a2 * 41) >> 10, tb = (b2 * 41) >> 10;
-                            C.t12 = T21[(((ty8 + ta) * 5 + si1) * 5 + (a2 / 5) % 5) * 5 + sj1];
-                            C.t21 = T21[(((tb * 8 + type) * 5 + (b2 / 5) % 5) * 5 + si1) * 5 + b2 % 5];
-                        }
-                        if (has(size_bits(4)) && uml >= 4) {
-                            const int c2 = L.cc[off(dd - 6, N) + i + 2];
-                            const int t2 = (c2 * 41) >> 10;
-                            C.t22 = T22[((((ty8 + t2) * 5 + si1) * 5 + c2 % 5) * 5 + (c2 / 5) % 5) * 5 + sj1];
-                        }
-                    }
-                    Acc a{INF16, INF16, INF16, INF16, INF16, INF16};
-                    const bool mk = constrained && __ballot(C.A < uml || C.B < uml) != 0;
-                    U.mk = mk;
-                    PSTAMP(9);
-                    if (sh == 2) mfe_block_s4(blk, U, C, a);
-                    else if (sh == 1) mfe_block_s2(blk, U, C, a);
-                    else mfe_block(blk, U, C, a);
-                    PSTAMP(10);
-                    u32 acc = pmin(pmin(a.s, padd(pmin(a.g0, a.g1), mmo)), pmin(padd(a.b, tau), padd(a.n, mo)));
-                    if (sh == 2) acc = pmin(acc, padd(a.e, C.r2 ? mo : tau));
-                    if (sh == 2) acc = fold_rows16(acc);
-                    if (sh >= 1) acc = fold_halves(acc);
-                    if (r == 0) {
-                        int *pp = L.part + (dd & 3) * 2 * NP + i;
-                        atomicMin(pp, sext_lo(acc));
-                        atomicMin(pp + NP, sext_hi(acc));
-                    }
-                }
-            }
-        }
+        block_partials<wid>(L, *TT, U, d, lane, sl, cPP, cwd, cmm, constrained, tauE, fsm5 PSTAMP_ARGS);
         cPP = nPP, cwd = nwd, cmm = nmm;
         PSTAMP(3);
-        // ---------------- M: split parts of qm for spans d and d+1 (lanes = cells x
-        // slices of the split points, mfe_cells.hip): min over t >= 5 of
-        // qm(i, i+t-1) + qm1(i+t, j), written to the span's slot for F
-        if (wid == mw[0] || wid == mw[1]) {
-            __builtin_amdgcn_s_setprio(PRIO_ROLE);
-            {
-                const int s = wid == mw[0] ? d : d + 1;
-                if (s >= 9 && s <= N - 3) {   // no split point below span 9
-                const int lo = qlo(s), hi = qhi(s);
-                const int Lm = lanesets(hi - lo + 1);
-                const int Tt = s - 4;
-                u32 *slot = L.mla + (s % 6) * NP;
-                for (int ls = 0; ls < Lm; ls++) {
-                    const int nc = min(WAVE, hi - lo + 1 - ls * WAVE);
-                    const int lc = nc <= 1 ? 0 : 32 - __clz(nc - 1);
-                    const int cst = 1 << lc, lsl = 6 - lc;
-                    const int c = lane & (cst - 1), rr = lane >> lc;
-                    int i = lo + ls * WAVE + c;
-                    const bool valid = c < nc;
-                    if (!valid) i = hi;
-                    const int j = i + s;
-                    const int nb = Tt - 4;                                  // split points t = 5..Tt
-                    const int bs = nb > 0 ? (nb + (1 << lsl) - 1) >> lsl : 0;
-                    u32 sp0 = INF16, sp1 = INF16;
-                    // split points in chunks of 16 and a last chunk of 16, 8 or 4 (bs is
-                    // uniform, so are the chunk shapes; round 5: +0.7 %, reads past a
-                    // slice's end cost as much as the ones in it on the M waves)
-                    auto chunk = [&](auto nconst, int t0) __attribute__((always_inline)) {
-                        constexpr int NR = decltype(nconst)::value;
-                        u32 av[NR], rv[NR];
-                        const uint32_t pa = aqm1 + uint32_t(colb(j) + i - 1 + t0) * 4u;
-                        const uint32_t pr = aqm + uint32_t(rowb(i, N) - 5 + t0) * 4u;
-                        if constexpr (NR == 16) {
-                            asm volatile(
-                                    "ds_read_b32 %0, %32 offset:0\n"
-                                    "ds_read_b32 %1, %32 offset:4\n"
-                                    "ds_read_b32 %2, %32 offset:8\n"
-                                    "ds_read_b32 %3, %32 offset:12\n"
-                                    "ds_read_b32 %4, %32 offset:16\n"
-                                    "ds_read_b32 %5, %32 offset:20\n"
-                                    "ds_read_b32 %6, %32 offset:24\n"
-                                    "ds_read_b32 %7, %32 offset:28\n"
-                                    "ds_read_b32 %8, %32 offset:32\n"
-                                    "ds_read_b32 %9, %32 offset:36\n"
-                                    "ds_read_b32 %10, %32 offset:40\n"
-                                    "ds_read_b32 %11, %32 offset:44\n"
-                                    "ds_read_b32 %12, %32 offset:48\n"
-                                    "ds_read_b32 %13, %32 offset:52\n"
-                                    "ds_read_b32 %14, %32 offset:56\n"
-                                    "ds_read_b32 %15, %32 offset:60\n"
-                                    "ds_read_b32 %16, %33 offset:0\n"
-                                    "ds_read_b32 %17, %33 offset:4\n"
-                                    "ds_read_b32 %18, %33 offset:8\n"
-                                    "ds_read_b32 %19, %33 offset:12\n"
-                                    "ds_read_b32 %20, %33 offset:16\n"
-                                    "ds_read_b32 %21, %33 offset:20\n"
-                                    "ds_read_b32 %22, %33 offset:24\n"
-                                    "ds_read_b32 %23, %33 offset:28\n"
-                                    "ds_read_b32 %24, %33 offset:32\n"
-                                    "ds_read_b32 %25, %33 offset:36\n"
-                                    "ds_read_b32 %26, %33 offset:40\n"
-                                    "ds_read_b32 %27, %33 offset:44\n"
-                                    "ds_read_b32 %28, %33 offset:48\n"
-                                    "ds_read_b32 %29, %33 offset:52\n"
-                                    "ds_read_b32 %30, %33 offset:56\n"
-                                    "ds_read_b32 %31, %33 offset:60\n"
-                                "s_waitcnt lgkmcnt(0)"
-                                : "=&v"(av[0]), "=&v"(av[1]), "=&v"(av[2]), "=&v"(av[3]), "=&v"(av[4]), "=&v"(av[5]), "=&v"(av[6]), "=&v"(av[7]), "=&v"(av[8]), "=&v"(av[9]), "=&v"(av[10]), "=&v"(av[11]), "=&v"(av[12]), "=&v"(av[13]), "=&v"(av[14]), "=&v"(av[15]), "=&v"(rv[0]), "=&v"(rv[1]), "=&v"(rv[2]), "=&v"(rv[3]), "=&v"(rv[4]), "=&v"(rv[5]), "=&v"(rv[6]), "=&v"(rv[7]), "=&v"(rv[8]), "=&v"(rv[9]), "=&v"(rv[10]), "=&v"(rv[11]), "=&v"(rv[12]), "=&v"(rv[13]), "=&v"(rv[14]), "=&v"(rv[15])
-                                : "v"(pa), "v"(pr)
-                                : "memory");
-                        } else if constexpr (NR == 4) {
-                            asm volatile(
-                                    "ds_read_b32 %0, %8 offset:0\n"
-                                    "ds_read_b32 %1, %8 offset:4\n"
-                                    "ds_read_b32 %2, %8 offset:8\n"
-                                    "ds_read_b32 %3, %8 offset:12\n"
-                                    "ds_read_b32 %4, %9 offset:0\n"
-                                    "ds_read_b32 %5, %9 offset:4\n"
-                                    "ds_read_b32 %6, %9 offset:8\n"
-                                    "ds_read_b32 %7, %9 offset:12\n"
-                                "s_waitcnt lgkmcnt(0)"
-                                : "=&v"(av[0]), "=&v"(av[1]), "=&v"(av[2]), "=&v"(av[3]), "=&v"(rv[0]), "=&v"(rv[1]), "=&v"(rv[2]), "=&v"(rv[3])
-                                : "v"(pa), "v"(pr)
-                                : "memory");
-                        } else {
-                            asm volatile(
-                                    "ds_read_b32 %0, %16 offset:0\n"
-                                    "ds_read_b32 %1, %16 offset:4\n"
-                                    "ds_read_b32 %2, %16 offset:8\n"
-                                    "ds_read_b32 %3, %16 offset:12\n"
-                                    "ds_read_b32 %4, %16 offset:16\n"
-                                    "ds_read_b32 %5, %16 offset:20\n"
-                                    "ds_read_b32 %6, %16 offset:24\n"
-                                    "ds_read_b32 %7, %16 offset:28\n"
-                                    "ds_read_b32 %8, %17 offset:0\n"
-                                    "ds_read_b32 %9, %17 offset:4\n"
-                                    "ds_read_b32 %10, %17 offset:8\n"
-                                    "ds_read_b32 %11, %17 offset:12\n"
-                                    "ds_read_b32 %12, %17 offset:16\n"
-                                    "ds_read_b32 %13, %17 offset:20\n"
-                                    "ds_read_b32 %14, %17 offset:24\n"
-                                    "ds_read_b32 %15, %17 offset:28\n"
-                                "s_waitcnt lgkmcnt(0)"
-                                : "=&v"(av[0]), "=&v"(av[1]), "=&v"(av[2]), "=&v"(av[3]), "=&v"(av[4]), "=&v"(av[5]), "=&v"(av[6]), "=&v"(av[7]), "=&v"(rv[0]), "=&v"(rv[1]), "=&v"(rv[2]), "=&v"(rv[3]), "=&v"(rv[4]), "=&v"(rv[5]), "=&v"(rv[6]), "=&v"(rv[7])
-                                : "v"(pa), "v"(pr)
-                                : "memory");
-                        }
-                        // reads past this slice's end belong to the next slice (a split point
-                        // counted twice leaves the minimum unchanged): only the row end Tt masks
-                        const int lim = Tt - t0;
-                        if (__ballot(lim < NR - 1) == 0) {
-#pragma unroll
-                            for (int k = 0; k < NR; k += 2) {
-                                sp0 = pmin(sp0, padd(rv[k], av[k]));
-                                sp1 = pmin(sp1, padd(rv[k + 1], av[k + 1]));
-                            }
-                        } else {
-#pragma unroll
-                            for (int k = 0; k < NR; k += 2) {
-                                sp0 = pmin(sp0, padd(rv[k], k <= lim ? av[k] : INF16));
-                                sp1 = pmin(sp1, padd(rv[k + 1], k + 1 <= lim ? av[k + 1] : INF16));
-                            }
-                        }
-                    };
-                    int t0 = 5 + rr * bs;
-                    for (int ch = 0; ch < (bs >> 4); ch++, t0 += 16) chunk(std::integral_constant<int, 16>{}, t0);
-                    const int rem = bs & 15;
-                    if (rem > 8) chunk(std::integral_constant<int, 16>{}, t0);
-                    else if (rem > 4) chunk(std::integral_constant<int, 8>{}, t0);
-                    else if (rem > 0) chunk(std::integral_constant<int, 4>{}, t0);
-                    u32 split = pmin(sp0, sp1);
-                    for (int k = cst; k < WAVE; k <<= 1) split = pmin(split, u32(__shfl_xor(int(split), k, WAVE)));
-                    if (valid && rr == 0) slot[i] = pfin(split);
-                }
-                }
-            }
-            __builtin_amdgcn_s_setprio(0);
-        }
+        if (wid == MW[0] || wid == MW[1]) split_rows(L, bd, wid == MW[0] ? d : d + 1, lane);
         PSTAMP(4);
-        // ---------------- Q: q5[j] for j = d-3, d-2 (qbm spans <= d-3 are final)
-        if (wid == Q_WAVE) {
-            const int j0 = d - 3, j1 = d - 2;
-            const bool w0 = j0 >= 5 && j0 <= N && (!incr || j0 >= m_lo - 1);
-            const bool w1 = j1 >= 5 && j1 <= N && (!incr || j1 >= m_lo - 1);
-            if (w0 || w1) {
-                __builtin_amdgcn_s_setprio(PRIO_ROLE);
-                // the last step of an odd N has j1 = N + 1 (w1 false): its chain reads
-                // column N instead, so no read leaves the tables (the result is unused)
-                const int j1r = j1 <= N ? j1 : N;
-                const int s0 = L.S[j0], s1 = L.S[j1r];
-                const int sp0 = (j0 < N) ? L.S[j0 + 1] : 5, sp1 = (j1r < N) ? L.S[j1r + 1] : 5;   // no dangle past N
-                u32 acc0 = INF16, acc1 = INF16;
-                for (int k0 = 1; k0 <= j1r - 4; k0 += WAVE) {
-                    const int kk = k0 + lane;
-                    const bool ok1 = kk <= j1r - 4, ok0 = kk <= j0 - 4;
-                    const int k = ok1 ? kk : 1;
-                    const int sk = L.S[k], skm = (k > 1) ? L.S[k - 1] : 5;
-                    const u32 q5k = L.q5[k - 1];
-                    const int ix1 = off(j1r - k, N) + k - 1;
-                    const int ix0 = off(max(j0 - k, 4), N) + k - 1;
-                    const u32 ex1 = L.dt[DT_EXT + ptype(sk, s1) * 36 + skm * 6 + sp1];
-                    const u32 ex0 = L.dt[DT_EXT + ptype(sk, s0) * 36 + skm * 6 + sp0];
-                    const u32 t1 = padd(padd(q5k, L.qbm[ix1]), padd(L.ct[CT_INVMM + L.cc[ix1]], ex1));
-                    const u32 t0 = padd(padd(q5k, L.qbm[ix0]), padd(L.ct[CT_INVMM + L.cc[ix0]], ex0));
-                    acc1 = pmin(acc1, ok1 ? t1 : INF16);
-                    acc0 = pmin(acc0, ok0 ? t0 : INF16);
-                }
-                const u32 red0 = wave_min(acc0), red1 = wave_min(acc1);
-                if (lane == 0) {
-                    u32 q0 = L.q5[j0];   // restored (refold) or initial when not recomputed
-                    if (w0) {
-                        q0 = pfin(pmin((L.up[j0] >= 1) ? L.q5[j0 - 1] : INF16, red0));
-                        L.q5[j0] = q0;
-                    }
-                    if (w1) L.q5[j1] = pfin(pmin((L.up[j1] >= 1) ? q0 : INF16, red1));
-                }
-                __builtin_amdgcn_s_setprio(0);
-            }
-        }
+        if (wid == Q_WAVE) q5_columns(L, bd, d, lane);
         PSTAMP(5);
         lds_barrier();
         PSTAMP(6);
@@ -1242,40 +1174,6 @@ __device__ __forceinline__ void mfe_pair_fold(const KArgs &ka, const DevScaled *
 #endif
 }
 
-// the fold's write-back and 16-bit range check (one copy for all waves)
-template <int NT, int NM>
-__device__ __forceinline__ void pair_finish(const KArgs &ka, const int *vs, const CP &L, const IncM &inc, u32 &z,
-                                            bool &bad) {
-    const int N = uni(ka.variants[vs[0]].N);
-    const int tid = threadIdx.x;
-    z = L.q5[N];
-    if (inc.dst) {   // this fold's tables: the next proposal's unchanged cells
-        const size_t C = size_t(ka.cells);
-        u32 *dp = inc.dst;
-        for (int k = tid; k < int(C); k += NT) {
-            dp[k] = L.qbm[k];
-            dp[C + k] = L.qm[k];
-            dp[2 * C + k] = L.qm1[k];
-        }
-        for (int k = tid; k <= N; k += NT) dp[3 * C + k] = L.q5[k];
-        const int C16 = (((N - 4) * (N - 3)) / 2 + 15) >> 4;
-        for (int k = tid; k < C16; k += NT) inc.cc_dst[k] = reinterpret_cast<const uint4 *>(L.cc)[k];
-    }
-    bool low = false;
-    const int C = ((N - 4) * (N - 3)) >> 1;
-    auto chk = [&](u32 x) {
-        const s16x2 q = sv(x);
-        low |= mfe16_inexact(q);
-    };
-    for (int k = tid; k < C; k += NT) {
-        chk(L.qbm[k]);
-        chk(L.qm[k]);
-        chk(L.qm1[k]);
-    }
-    for (int k = tid; k <= N; k += NT) chk(L.q5[k]);
-    bad = block_or(L.flag + 1, low);
-}
-
 // the fold instance of wave w (one per wave: mfe_pair_fold's WID)
 template <int NT, int NM, int... Ws>
 __device__ __forceinline__ void pair_fold_wave(std::integer_sequence<int, Ws...>, int w, const KArgs &ka,
@@ -1285,7 +1183,6 @@ __device__ __forceinline__ void pair_fold_wave(std::integer_sequence<int, Ws...>
     ((w == Ws ? (mfe_pair_fold<NT, NM, Ws>(ka, XS, TT, vs, L, inc, constrained, sst), 0) : 0), ...);
 }
 
-constexpr int MFE_WPE = (2 * NWV + 3) / 4;
 template <int NT, int NM>
 __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MFE_WPE, MFE_WPE)))
 mfe_pair_kernel(const KArgs ka, const DevScaled *__restrict__ XS, const DevTables *__restrict__ TT, const uint8_t *seqs,
@@ -1303,41 +1200,21 @@ mfe_pair_kernel(const KArgs ka, const DevScaled *__restrict__ XS, const DevTable
     const int vs[2] = {ka.groups2[2 * g], ka.groups2[2 * g + 1]};
     IncM inc{nullptr, nullptr, 0, 0, nullptr, nullptr};
     if (ka.tab) {
-        const size_t Gf = inc_group_floats(ka.cells, ka.Nmax, 1);
-        const int cur = wr.cur;
-        float *base = ka.tab + size_t(w) * 2 * ka.tab_slot;
-        inc.dst = reinterpret_cast<u32 *>(base + size_t(1 - cur) * ka.tab_slot + size_t(g) * Gf);
-        const size_t cco = inc_cc_offset(ka.cells, ka.Nmax, ng, g);
-        inc.cc_dst = reinterpret_cast<uint4 *>(base + size_t(1 - cur) * ka.tab_slot + cco);
+        inc = inc_slots(ka, w, g, wr.cur);
         // a sibling group may clear tab_valid[w] on overflow while this one reads it:
         // either value is correct (an incremental refold equals a fold from scratch)
-        if (wr.valid && wr.c0 >= 0) {
-            const int lb = ka.variants[vs[0]].before_len;
-            inc.src = reinterpret_cast<const u32 *>(base + size_t(cur) * ka.tab_slot + size_t(g) * Gf);
-            inc.cc_src = reinterpret_cast<const uint4 *>(base + size_t(cur) * ka.tab_slot + cco);
-            inc.m_lo = wr.c0 + 1 + lb;
-            inc.m_hi = wr.c1 + 1 + lb;
-        }
+        if (wr.valid && wr.c0 >= 0)
+            inc_refold(inc, ka, w, g, wr.cur, wr.c0, wr.c1, ka.variants[vs[0]].before_len);
     }
-    u32 z = INF16;
-    bool bad = false;
     unsigned long long sst[7] = {0, 0, 0, 0, 0, 0, 0};
     const bool constrained = pair_setup<NT, NM>(ka, XS, TT, vs, seqs + size_t(w) * ka.Nraw, L, inc, sst);
     pair_fold_wave<NT, NM>(std::make_integer_sequence<int, NWV>{}, uni(int(threadIdx.x) / WAVE), ka, XS, TT, vs, L,
                            inc, constrained, sst);
-    pair_finish<NT, NM>(ka, vs, L, inc, z, bad);
-    if (threadIdx.x == 0) {
-        const s16x2 q = sv(z);
-        const int hv[2] = {q.x, q.y};
-        for (int h = 0; h < 2; h++) {
-            const double e = hv[h] >= 0x4000 ? double(INFINITY) : static_cast<double>(hv[h]) / 100.0;
-            gout[size_t(w) * ka.n_variants + vs[h]] = static_cast<float>(e);
-        }
-        if (bad && ka.ovf) {
-            ka.ovf[w] = 1;
-            if (ka.tab) ka.tab_valid[w] = 0;
-        }
-    }
+    // the fold's write-back and 16-bit range check (one copy for all waves)
+    const int N = uni(ka.variants[vs[0]].N);
+    const u32 z = L.q5[N];
+    const bool bad = block_or(L.flag + 1, fold_writeback<NT>(ka, L, inc, N));   // (mfe_cells.hip: __syncthreads_or)
+    if (threadIdx.x == 0) fold_result(ka, w, vs, gout, z, bad);
 }
 
 template <int NM>

@@ -88,12 +88,9 @@ def test_pair_partitions_skip_stack_and_bulge1():
     """The pair kernel's blocks hold loop sizes 2..30 once each (the stack and
     bulge-1 shapes run in its finalize, mfe_pair.hip) and add the per-lane
     diagonal offset hb * u to every inner-cell address."""
-    G.PAIR = True
-    try:
-        for S in (1, 2, 4):
-            blocks, load = G.partition(S)
-            assert sorted(u for b in blocks for u in b) == list(range(2, G.MAXLOOP + 1)), S
-        pre = G.sliced_parts(17, 4, "a")[0]
-        assert "off(dd - 19, U.N) + ci + hb * 17" in pre[0]
-    finally:
-        G.PAIR = False
+    pair = G.variant(True)
+    for S in (1, 2, 4):
+        blocks, load = G.partition(S, pair)
+        assert sorted(u for b in blocks for u in b) == list(range(2, G.MAXLOOP + 1)), S
+    pre = G.sliced_parts(17, 4, "a", pair)[0]
+    assert "off(dd - 19, U.N) + ci + hb * 17" in pre[0]

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Generate addapt_amd/csrc/mfe_blocks.inc: the interior-loop shapes of the
-lanes = cells MFE kernel (mfe_cells.hip) as straight-line code.
+"""Generate addapt_amd/csrc/mfe_blocks.inc and mfe_pair_blocks.inc: the
+interior-loop shapes of the lanes = cells MFE kernels (mfe_cells.hip,
+mfe_pair.hip) as straight-line code.
 
 A closing pair (i, j) reaches an inner pair (p, q) = (i+1+u1, j-1-u2) through a
 loop of size u = u1 + u2 <= 30 (ViennaRNA MAXLOOP; E_IntLoop cases restated in
@@ -22,6 +23,8 @@ Shape kinds (accumulator):
 """
 import os
 import sys
+from collections import namedtuple
+
 
 def out_dir():
     """addapt_amd/csrc, or ADX_GEN_OUT (tests regenerate into a scratch directory)."""
@@ -30,13 +33,7 @@ def out_dir():
 
 
 MAXLOOP = 30
-# PAIR: the blocks of the two-diagonals-per-barrier kernel (mfe_pair.hip) --
-# loop sizes u >= 2 only (the stack and bulge-1 shapes run in its finalize), and
-# a lane-set holds cells of two diagonals d, d+1: a lane's inner cells sit at
-# off(d - 2 - u) + ci + hb * u, with ci = i + hb * (N - d + 2) and hb = 1 on the
-# lanes of diagonal d + 1 (per-lane, set once per lane-set)
-PAIR = False
-NBLK = int(os.environ.get("ADX_GEN_NBLK", "7"))   # block waves 0..NBLK-1 (wave 7 folds the multiloop qm / mla)
+NBLK = 7           # block waves 0..6 of both kernels (wave 7: the multiloop qm / mla, or the finalize)
 SCHED_CHUNK = 1000 # shapes per scheduling window (whole loop sizes)
 KSAT = 5           # nin[k] == nin[KSAT] for k >= KSAT (checked on the host)
 
@@ -91,51 +88,61 @@ def scost(u, S):
 # qm1 column minima on wave 3, the list + records on wave 4 (q5 runs on the qm
 # wave 7, which has slack: 1.248M -> 1.266M MC steps/s; finalize on wave 1
 # instead of 6: +0.7-0.9 %; profiles/r04y_ab_roles.txt, r04z_ab_roles.txt)
-ROLES4 = "1:8,3:5,4:10" if NBLK == 7 else ""   # NBLK <= 4: the roles have waves of their own
+ROLES4 = "1:8,3:5,4:10"
 # pair kernel (mfe_pair.hip; cycles from tools/mfe_pair_stamps.py at ~4k per
 # unit): the split parts of span d on wave 0 and of d+1 on wave 2, q5 of two
 # columns on wave 3, the lists on wave 1 (round 5; wave 4 before), the finalize's second lane-set
 # (spans < 38) on wave 6; its first lane-set has wave 7 to itself
 PAIR_ROLES4 = "0:22,1:22,2:22,3:16,6:5"
 
+# Which file is generated.  pair: the blocks of the two-diagonals-per-barrier
+# kernel (mfe_pair.hip) -- loop sizes u >= 2 only (the stack and bulge-1 shapes
+# run in its finalize), and a lane-set holds cells of two diagonals d, d+1: a
+# lane's inner cells sit at off(d - 2 - u) + ci + hb * u, with
+# ci = i + hb * (N - d + 2) and hb = 1 on the lanes of diagonal d + 1 (per-lane,
+# set once per lane-set).  nblk: block waves.  roles4: "wave:cost,..." of the
+# one-wave roles
+Variant = namedtuple("Variant", "pair nblk roles4")
 
-def umin():
-    return 2 if PAIR else 0
+
+def variant(pair):
+    """The cells or the pair variant (ADX_GEN_ROLES4 / ADX_GEN_PAIR_ROLES4
+    override the role costs: tools/build_variant.py)."""
+    roles = os.environ.get("ADX_GEN_PAIR_ROLES4", PAIR_ROLES4) if pair else os.environ.get("ADX_GEN_ROLES4", ROLES4)
+    return Variant(pair, NBLK, roles)
 
 
-def role_loads(S):
-    """Per-wave cost of the roles (ADX_GEN_ROLES4 overrides, "wave:cost,...").
-    Only the 4-lanes-per-cell partition uses them: it serves ~96 % of an MC
-    refold's diagonals, the other two keep equal block costs."""
-    init = [0] * NBLK
-    env = "ADX_GEN_PAIR_ROLES4" if PAIR else "ADX_GEN_ROLES4"
-    spec = os.environ.get(env, PAIR_ROLES4 if PAIR else ROLES4) if S == 4 else ""
-    for item in filter(None, spec.split(",")):
+def role_loads(v, S):
+    """Per-wave cost of the roles.  Only the 4-lanes-per-cell partition uses
+    them: it serves ~96 % of an MC refold's diagonals, the other two keep equal
+    block costs."""
+    init = [0] * v.nblk
+    for item in filter(None, (v.roles4 if S == 4 else "").split(",")):
         w, c = item.split(":")
         init[int(w)] = int(c)
     return init
 
 
-def partition(S=1):
-    # greedy LPT over loop sizes, largest first; ties keep small u spread out
-    sizes = sorted(range(umin(), MAXLOOP + 1), key=lambda u: (-scost(u, S), -ucost(u)))
-    blocks = [[] for _ in range(NBLK)]
-    load = role_loads(S)
+def partition(S=1, v=None):
+    # greedy LPT over loop sizes, largest first; ties keep small u spread out (v: default cells)
+    v = v or variant(False)
+    sizes = sorted(range(2 if v.pair else 0, MAXLOOP + 1), key=lambda u: (-scost(u, S), -ucost(u)))
+    blocks = [[] for _ in range(v.nblk)]
+    load = role_loads(v, S)
     for u in sizes:
-        b = min(range(NBLK), key=lambda k: (load[k], len(blocks[k])))
+        b = min(range(v.nblk), key=lambda k: (load[k], len(blocks[k])))
         blocks[b].append(u)
         load[b] += scost(u, S)
     return [sorted(b) for b in blocks], load
 
 
 ASM_CHUNK = 24   # DP reads per inline-asm batch (1 VGPR per read)
-# sliced modes whose blocks get a batched path for spans that reach every loop
+# the 4-lanes-per-cell blocks get a batched path for spans that reach every loop
 # size of the block (umax >= its largest u): the sizes' reads in batches of at
 # most FULL_READS per lane, one LDS round trip each instead of one per size
-# (4 lanes per cell: 1.013M -> 1.054M MC steps/s; larger batches spill, and
-# the 2-lanes path spills 40 VGPRs with it)
-FULL_READS = int(os.environ.get("ADX_GEN_FULL_READS", "24"))
-FULL_BATCH = tuple(int(x) for x in os.environ.get("ADX_GEN_FULL", "4").split(",") if x)
+# (1.013M -> 1.054M MC steps/s; larger batches spill, and the 2-lanes path
+# spills 40 VGPRs with it)
+FULL_READS = 24
 
 
 TABK = ("i11", "i12", "i21", "i22")
@@ -144,7 +151,6 @@ TABK = ("i11", "i12", "i21", "i22")
 # read row k (|2 u1 - u| < KSAT for some slice) take them from a per-lane LDS
 # table (mfe_cells.hip CL::e4, slot q at byte 16 q + 4 r for slice r) read in the
 # batch, instead of a per-lane select among the record's scalar values
-ETAB4 = os.environ.get("ADX_GEN_ETAB4", "1") == "1"
 
 
 def gen_rows(u, S):
@@ -189,7 +195,7 @@ def plateau_min(vals, e, ind):
             nxt.append(vals[-1])
         vals = nxt
     lines.append(ind + "a.g0 = pmin(a.g0, padd(%s, %s));" % (vals[0], e))
-    return ["        {"] + lines + ["        }"] if False else [ind[:-4] + "{"] + lines + [ind[:-4] + "}"]
+    return [ind[:-4] + "{"] + lines + [ind[:-4] + "}"]
 
 
 def emit_group_asm(u, out):
@@ -289,7 +295,7 @@ def emit_table_fin(blk, out):
     out.append("    return;")
 
 
-def sliced_parts(u, S, t):
+def sliced_parts(u, S, t, v=None):
     """One loop size of a sliced block, variable names suffixed by t: address
     lines, declarations, asm reads/outputs/inputs and the arithmetic after the
     batch.  Loop sizes u >= 4 spread their edge shapes over the slices: with
@@ -297,11 +303,12 @@ def sliced_parts(u, S, t):
     on 2, 3: accumulator a.e, the outer term per slice is added by the caller),
     with S = 2 slice r reads the bulge n1 = C.eb * u and the 1 x n loop
     n1 = C.ea + C.eb * u."""
+    v = v or variant(False)
     ed = edges(u)
     spec = [u1 for u1 in range(u + 1) if kind(u1, u - u1) != "gen" and u1 not in ed]
     gen = [u1 for u1 in range(u + 1) if kind(u1, u - u1) == "gen"]
     pre, decl, lines, outs, ins, post = [], [], [], [], [], []
-    pre.append("const int o%s = off(dd - %d, U.N) + ci%s;" % (t, u + 2, (" + hb * %d" % u) if PAIR else ""))
+    pre.append("const int o%s = off(dd - %d, U.N) + ci%s;" % (t, u + 2, (" + hb * %d" % u) if v.pair else ""))
     pre.append("const uint32_t qa%s = U.aq + uint32_t(o%s) * 4u, ka%s = U.ac + uint32_t(o%s);" % (t, t, t, t))
     ins += ['[qa%s] "v"(qa%s)' % (t, t), '[ka%s] "v"(ka%s)' % (t, t)]
     V = lambda u1: "v%d%s" % (u1, t)
@@ -342,7 +349,7 @@ def sliced_parts(u, S, t):
             lines.append("ds_read_b32 %%[w%d%s], %%[qg%s] offset:%d" % (k, t, t, 4 * S * k))
             outs.append('[w%d%s] "=&v"(w%d%s)' % (k, t, k, t))
     etab = []   # rows k whose energies come from the per-lane table
-    if ETAB4 and S == 4:
+    if S == 4:
         for k in range(nk):
             if (u, k) in E4_SLOT:
                 etab.append(k)
@@ -363,10 +370,10 @@ def sliced_parts(u, S, t):
         post.append("    %s = (%d >= ml && %d <= mh) ? %s : INF16;" % (V(u1), u1, u1, V(u1)))
     for nm, _, _ in eds:
         post.append("    v%s%s = (n%s%s >= ml && n%s%s <= mh) ? v%s%s : INF16;" % ((nm, t) * 4))
-    if PAIR and nk:   # the slice offset folded into the bounds once (no per-position lane constants)
+    if v.pair and nk:   # the slice offset folded into the bounds once (no per-position lane constants)
         post.append("    const int gl = ml - rr, gh = mh - rr;")
     for k in range(nk):
-        if PAIR:
+        if v.pair:
             post.append("    w%d%s = (%d >= gl && %d <= gh) ? w%d%s : INF16;" % (k, t, gen[0] + S * k, gen[0] + S * k, k, t))
         else:
             post.append("    w%d%s = (%d + rr >= ml && %d + rr <= mh) ? w%d%s : INF16;" % (k, t, gen[0] + S * k, gen[0] + S * k, k, t))
@@ -425,9 +432,9 @@ def sliced_parts(u, S, t):
     return pre, decl, lines, outs, ins, post
 
 
-def emit_sliced_batch(groups, S, out, ind):
+def emit_sliced_batch(v, groups, S, out, ind):
     """One inline-asm read batch for the loop sizes in groups, then their arithmetic."""
-    parts = [sliced_parts(u, S, t) for u, t in groups]
+    parts = [sliced_parts(u, S, t, v) for u, t in groups]
     out.append(ind + "{   // u = %s (%d slices)" % (", ".join(str(u) for u, _ in groups), S))
     for p in parts:
         out.extend(ind + "    " + x for x in p[0] + p[1])
@@ -446,20 +453,20 @@ def emit_sliced_batch(groups, S, out, ind):
     out.append(ind + "MFE_SCHED_BARRIER();")
 
 
-def emit_block_cells_sliced(blk, S, out):
+def emit_block_cells_sliced(v, blk, S, out):
     """Inline-asm path of one block with S lanes per cell (S = 2, 4): lane slice
     r = 0..S-1 reads the generic shapes u1 = 2 + r + S*k of each loop size (one
     per-lane base + immediate offsets), so a diagonal with <= 64/S pairable cells
     runs the generic shapes in 1/S of the instructions.  Every slice also runs
     the special shapes (counting a shape in several slices leaves the minimum
     unchanged); the caller folds a.g0 / a.g1 across the slices."""
-    if S in FULL_BATCH:
+    if S == 4:
         # every loop size of the block fits the span: the whole block's reads in
         # one batch (one LDS round trip, then one for the dependent code reads)
         out.append("    if (um >= %d) {" % max(blk))
         groups, cur, nrd = [], [], 0
         for u in blk:   # batches of at most FULL_READS reads per lane
-            r = len(sliced_parts(u, S, "x")[2])
+            r = len(sliced_parts(u, S, "x", v)[2])
             if cur and nrd + r > FULL_READS:
                 groups.append(cur)
                 cur, nrd = [], 0
@@ -467,38 +474,30 @@ def emit_block_cells_sliced(blk, S, out):
             nrd += r
         groups.append(cur)
         for g in groups:
-            emit_sliced_batch(g, S, out, "        ")
+            emit_sliced_batch(v, g, S, out, "        ")
         out.append("        goto fin;")
         out.append("    }")
     for u in blk:
         out.append("    if (um < %d) goto fin;" % u)
-        emit_sliced_batch([(u, "a")], S, out, "    ")
+        emit_sliced_batch(v, [(u, "a")], S, out, "    ")
     emit_table_fin(blk, out)
 
 
-# the pair kernel's block waves (ADX_GEN_PAIR_NBLK; its output file name
-# ADX_GEN_PAIR_OUT, for A/B builds of another wave count)
-PAIR_NBLK = int(os.environ.get("ADX_GEN_PAIR_NBLK", str(NBLK)))
-
-
 def main():
-    global PAIR, NBLK
-    cells_nblk = NBLK
     only = os.environ.get("ADX_GEN_ONLY")   # "pair" / "cells": one file
-    for PAIR in (False, True):
-        if only and only != ("pair" if PAIR else "cells"):
-            continue
-        NBLK = PAIR_NBLK if PAIR else cells_nblk
-        emit_file()
+    for pair in (False, True):
+        if not only or only == ("pair" if pair else "cells"):
+            emit_file(variant(pair))
 
 
-def emit_file():
-    blocks, load = partition()
+def emit_file(v):
+    """mfe_pair_blocks.inc (v.pair) or mfe_blocks.inc in out_dir()."""
+    blocks, load = partition(1, v)
     out = []
     out.append("// GENERATED by tools/gen_mfe_blocks.py -- do not edit.")
-    if PAIR:
+    if v.pair:
         out.append("// Pair variant (mfe_pair.hip): loop sizes u >= 2, per-lane diagonal offset hb.")
-    out.append("// Interior-loop shapes of mfe_cells.hip in %d blocks of LDS cost %s." % (NBLK, load))
+    out.append("// Interior-loop shapes of mfe_cells.hip in %d blocks of LDS cost %s." % (v.nblk, load))
     out.append("// Block b: loop sizes %s" % "; ".join("%d:%s" % (b, blk) for b, blk in enumerate(blocks)))
     out.append("")
     for b, blk in enumerate(blocks):
@@ -507,7 +506,7 @@ def emit_file():
         # above the block switch it would stay live across all blocks)
         out.append("    int ci = C.i, dd = U.d, um = U.umax;")
         out.append('    asm volatile("" : "+v"(ci));')
-        if PAIR:
+        if v.pair:
             out.append('    int hb = C.hb;')
             out.append('    asm volatile("" : "+v"(hb));')
         out.append('    asm volatile("" : "+s"(dd), "+s"(um));')
@@ -517,7 +516,7 @@ def emit_file():
         for u in blk:
             out.append("    if (um < %d) goto fin;" % u)
             out.append("    {   // u = %d (batched reads)" % u)
-            out.append("        const int o = off(dd - %d, U.N) + ci%s;" % (u + 2, (" + hb * %d" % u) if PAIR else ""))
+            out.append("        const int o = off(dd - %d, U.N) + ci%s;" % (u + 2, (" + hb * %d" % u) if v.pair else ""))
             out.append("        const uint32_t qa = U.aq + uint32_t(o) * 4u, ka = U.ac + uint32_t(o);")
             nspec = sum(1 for u1 in range(u + 1) if kind(u1, u - u1) != "gen")
             out.append("        uint32_t gk[6], fb = 0, f1n = 0, cs[%d];" % max(1, nspec))
@@ -530,32 +529,32 @@ def emit_file():
         out.append("")
     out.append("__device__ __forceinline__ void mfe_block(int b, const BUni &U, const BCell &C, Acc &a) {")
     out.append("    switch (b) {")
-    for b in range(NBLK):
+    for b in range(v.nblk):
         out.append("        case %d: mfe_blk%d(U, C, a); return;" % (b, b))
     out.append("        default: return;")
     out.append("    }")
     out.append("}")
     out.append("")
     for S in (2, 4):
-        sblocks, sload = partition(S)
+        sblocks, sload = partition(S, v)
         out.append("// %d lanes per cell: blocks of LDS cost %s: %s" % (S, sload, "; ".join("%d:%s" % (b, blk) for b, blk in enumerate(sblocks))))
         for b, blk in enumerate(sblocks):
             out.append("__device__ __forceinline__ void mfe_blk%d_s%d(const BUni &U, const BCell &C, Acc &a) {" % (b, S))
             out.append("    int ci = C.i, dd = U.d, um = U.umax, ea = C.ea, eb = C.eb;")
             out.append('    asm volatile("" : "+v"(ci), "+v"(ea), "+v"(eb));')
-            if PAIR:
+            if v.pair:
                 out.append('    int hb = C.hb;')
                 out.append('    asm volatile("" : "+v"(hb));')
             out.append('    asm volatile("" : "+s"(dd), "+s"(um));')
             out.append('    const kc_u32 *kg = kconst(U.kg);   // opaque: the record loads stay at their use (s_load, SGPRs)')
             out.append('    asm volatile("" : "+s"(kg));')
             emit_table_decl(blk, out)
-            emit_block_cells_sliced(blk, S, out)
+            emit_block_cells_sliced(v, blk, S, out)
             out.append("}")
             out.append("")
         out.append("__device__ __forceinline__ void mfe_block_s%d(int b, const BUni &U, const BCell &C, Acc &a) {" % S)
         out.append("    switch (b) {")
-        for b in range(NBLK):
+        for b in range(v.nblk):
             out.append("        case %d: mfe_blk%d_s%d(U, C, a); return;" % (b, b, S))
         out.append("        default: return;")
         out.append("    }")
@@ -564,7 +563,7 @@ def emit_file():
     # which blocks hold the table shapes (prefetch only there), per lanes per cell
     for S in (1, 2, 4):
         tb = 0
-        for b, blk in enumerate(partition(S)[0]):
+        for b, blk in enumerate(partition(S, v)[0]):
             if any(u in (2, 3, 4) for u in blk):
                 tb |= 1 << b
         out.append("constexpr unsigned MFE_TABLE_BLOCKS%s = 0x%xu;   // blocks with 1x1 / 1x2 / 2x1 / 2x2 shapes%s"
@@ -574,23 +573,22 @@ def emit_file():
     rows = []
     for S in (1, 2, 4):
         wb = [-1] * (MAXLOOP + 1)
-        for b, blk in enumerate(partition(S)[0]):
+        for b, blk in enumerate(partition(S, v)[0]):
             for u in blk:
                 wb[u] = b
         rows.append("{%s}" % ", ".join(str(x) for x in wb))
     out.append("constexpr signed char MFE_SIZE_BLOCK[3][%d] = {%s};   // [log2 lanes per cell][u] -> block"
                % (MAXLOOP + 1, ", ".join(rows)))
-    sl = e4_slots() if ETAB4 else []
+    sl = e4_slots()
     out.append("// per-lane generic energies of the 4-lanes-per-cell blocks: slot q holds loop size")
     out.append("// MFE_E4_U[q] and, for slice r, the Ninio index MFE_E4_A[q][r] (-1: no shape)")
     out.append("constexpr int MFE_E4_SLOTS = %d;" % len(sl))
-    out.append("constexpr signed char MFE_E4_U[%d] = {%s};" % (max(1, len(sl)), ", ".join(str(u) for u, _, _ in sl) or "0"))
-    out.append("constexpr signed char MFE_E4_A[%d][4] = {%s};" % (max(1, len(sl)), ", ".join(
-        "{%s}" % ", ".join(str(-1 if a is None else a) for a in row) for _, _, row in sl) or "{-1, -1, -1, -1}"))
-    out.append("constexpr int MFE_NBLK = %d;" % NBLK)
+    out.append("constexpr signed char MFE_E4_U[%d] = {%s};" % (len(sl), ", ".join(str(u) for u, _, _ in sl)))
+    out.append("constexpr signed char MFE_E4_A[%d][4] = {%s};" % (len(sl), ", ".join(
+        "{%s}" % ", ".join(str(-1 if a is None else a) for a in row) for _, _, row in sl)))
+    out.append("constexpr int MFE_NBLK = %d;" % v.nblk)
     out.append("constexpr int MFE_KSAT = %d;   // generic loops: nin[k] == nin[MFE_KSAT] for k >= MFE_KSAT" % KSAT)
-    path = os.path.join(out_dir(), os.environ.get("ADX_GEN_PAIR_OUT", "mfe_pair_blocks.inc") if PAIR
-                        else "mfe_blocks.inc")
+    path = os.path.join(out_dir(), "mfe_pair_blocks.inc" if v.pair else "mfe_blocks.inc")
     with open(path, "w") as f:
         f.write("\n".join(out) + "\n")
     print("blocks:", blocks, "load:", load, file=sys.stderr)
