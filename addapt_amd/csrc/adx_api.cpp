@@ -427,6 +427,8 @@ struct Problem {
     DevBuf<int> dOrder;          // launch order of a rescore's folds (KArgs::order, order_kernel)
     DevBuf<uint8_t> dCls;        // the folds' weight classes (KArgs::ocls, the proposals' or a rescore's)
     DevBuf<int> dTrace;          // c / fm / fm1 scratch of mfe_trace_kernel, one launch chunk
+    DevBuf<double> dSample;      // qb / qm / qm1 / q5 scratch of pf_fill_kernel, one launch chunk
+    float sample_fill_ms = 0.f, sample_draw_ms = 0.f;   // the last sample() call, from HIP events
     size_t tab_slot = 0;
     bool state_on = false;   // set for MC launches only (not for adx_score_batch)
     std::unique_ptr<DevTables> hT;
@@ -668,6 +670,73 @@ struct Problem {
         return ADX_OK;
     }
 
+    // n_samples structures drawn from the ensemble of each of W sequences (device
+    // codes) for one variant, to HOST buffers: structures[W][n_samples][variants[v].N]
+    // chars, energies[W] (optional).  pf_sample.hip; touches no fold state.
+    // chunk > 0 overrides the sequences per launch (the results do not depend on it).
+    adx_status sample(const char *who, const uint8_t *dseqs, int W, int v, int n_samples, uint64_t seed,
+                      char *structures, float *energies, int chunk = 0) {
+        const KArgs ka = kargs();
+        const size_t L = size_t(variants[v].N);
+        SamplePlan plan = pf_sample_plan(ka, int(L), W, n_samples);
+        if (chunk > 0) plan.seqs = std::min(plan.seqs, chunk);
+        const size_t slice = pf_sample_slice_doubles(ka);
+        if (dSample.n < size_t(plan.seqs) * slice) HIP_TRY(dSample.alloc(size_t(plan.seqs) * slice));
+        DevBuf<char> dout;
+        DevBuf<float> de;
+        DevBuf<int> dflag;
+        HIP_TRY(dout.alloc(size_t(plan.seqs) * plan.samples * L));
+        HIP_TRY(de.alloc(W));
+        HIP_TRY(dflag.alloc(1));
+        HIP_TRY(hipMemsetAsync(dflag.p, 0, sizeof(int), stream));
+        hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+        struct Drop {
+            hipEvent_t *ev;
+            ~Drop() {
+                for (int k = 0; k < 3; k++)
+                    if (ev[k]) (void)hipEventDestroy(ev[k]);
+            }
+        } drop{ev};
+        for (auto &e : ev) HIP_TRY(hipEventCreate(&e));
+        sample_fill_ms = sample_draw_ms = 0.f;
+        for (int w0 = 0; w0 < W; w0 += plan.seqs) {
+            const int n = std::min(plan.seqs, W - w0);
+            HIP_TRY(hipEventRecord(ev[0], stream));
+            HIP_TRY(launch_pf_fill(ka, v, dseqs, w0, n, dSample.p, de.p, stream));
+            HIP_TRY(hipEventRecord(ev[1], stream));
+            float fill = 0.f;
+            for (int k0 = 0; k0 < n_samples; k0 += plan.samples) {
+                const int nk = std::min(plan.samples, n_samples - k0);
+                if (k0 > 0) HIP_TRY(hipEventRecord(ev[1], stream));
+                HIP_TRY(launch_pf_sample(ka, v, dseqs, w0, n, dSample.p, k0, nk, seed, dout.p, dflag.p, stream));
+                HIP_TRY(hipEventRecord(ev[2], stream));
+                if (nk == n_samples) {   // the chunk's rows are contiguous on both sides
+                    HIP_TRY(hipMemcpyAsync(structures + size_t(w0) * n_samples * L, dout.p, size_t(n) * nk * L,
+                                           hipMemcpyDeviceToHost, stream));
+                } else {
+                    for (int r = 0; r < n; r++)
+                        HIP_TRY(hipMemcpyAsync(structures + (size_t(w0 + r) * n_samples + k0) * L,
+                                               dout.p + size_t(r) * nk * L, size_t(nk) * L, hipMemcpyDeviceToHost,
+                                               stream));
+                }
+                HIP_TRY(hipStreamSynchronize(stream));   // dout is reused by the next launch
+                float ms = 0.f;
+                if (k0 == 0) HIP_TRY(hipEventElapsedTime(&fill, ev[0], ev[1]));
+                HIP_TRY(hipEventElapsedTime(&ms, ev[1], ev[2]));
+                sample_draw_ms += ms;
+            }
+            sample_fill_ms += fill;
+        }
+        int flag = 0;
+        HIP_TRY(hipMemcpyAsync(&flag, dflag.p, sizeof(int), hipMemcpyDeviceToHost, stream));
+        if (energies) HIP_TRY(hipMemcpyAsync(energies, de.p, sizeof(float) * W, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (flag)
+            return fail(ADX_EHIP, "%s: a sample reached the sampler's loop bound (inconsistent tables); its "
+                        "structure is all '.'", who);
+        return ADX_OK;
+    }
+
     // the per-walker buffers a fold of W walkers writes (grow-only)
     adx_status prepare(int W) {
         adx_status so = ensure_ovf(W);
@@ -892,6 +961,21 @@ extern "C" adx_status adx_fold_mfe_structure(adx_fold *f, char *structure, float
     HIP_TRY(hipStreamSynchronize(pb.stream));
     structure[N] = 0;
     return ADX_OK;
+}
+
+extern "C" adx_status adx_fold_sample_structures(adx_fold *f, int n_samples, uint64_t seed, char *structures,
+                                                 float *energy) {
+    if (!f || !structures) return fail(ADX_EINVAL, "adx_fold_sample_structures: null argument");
+    if (n_samples < 1) return fail(ADX_EINVAL, "adx_fold_sample_structures: n_samples %d < 1", n_samples);
+    Problem pb;
+    // the default scale serves: pf_fill_kernel sums in FP64, which the factors of
+    // no sequence of <= NMAX bases leave, so there is no calibration loop here
+    adx_status s = fold_problem(f, 0, pb);
+    if (s) return s;
+    const std::vector<uint8_t> codes = encode(f->seq);
+    DevBuf<uint8_t> dseq;
+    HIP_TRY(dseq.upload(codes.data(), codes.size(), pb.stream));
+    return pb.sample("adx_fold_sample_structures", dseq.p, 1, 0, n_samples, seed, structures, energy);
 }
 
 extern "C" adx_status adx_fold_bpp(adx_fold *f, int i, int j, double *prob) {
@@ -1618,6 +1702,50 @@ extern "C" adx_status adx_walkers_mfe_structures(adx_ctx *c, int variant, char *
     if (c->pb.mode == ADX_FOLD_MFE && c->W <= 0)
         return fail(ADX_ESTATE, "adx_walkers_mfe_structures before adx_walkers_init");
     return mfe_structures(c, "adx_walkers_mfe_structures", c->cur_seq.p, c->W, variant, structures, energies);
+}
+
+// n_samples structures per device sequence for variant v, drawn from its ensemble
+static adx_status sample_structures(adx_ctx *c, const char *who, const uint8_t *dseqs, int W, int v, int n_samples,
+                                    uint64_t seed, char *structures, float *energies) {
+    Problem &pb = c->pb;
+    if (pb.mode != ADX_FOLD_PF)
+        return fail(ADX_EUNSUPPORTED, "%s: ADX_FOLD_PF contexts only (an MFE context holds no Boltzmann "
+                    "factors; use adx_fold_sample_structures)", who);
+    if (v < 0 || v >= static_cast<int>(pb.variants.size()))
+        return fail(ADX_EINVAL, "%s: variant %d outside [0, %zu)", who, v, pb.variants.size());
+    if (n_samples < 1) return fail(ADX_EINVAL, "%s: n_samples %d < 1", who, n_samples);
+    const size_t L = size_t(pb.variants[v].N);
+    if (size_t(W) > SIZE_MAX / L / size_t(n_samples))
+        return fail(ADX_EINVAL, "%s: %d x %d structures of %zu chars overflow", who, W, n_samples, L);
+    return pb.sample(who, dseqs, W, v, n_samples, seed, structures, energies);
+}
+
+extern "C" adx_status adx_sample_structures_batch(adx_ctx *c, int W, const char *seqs, int variant, int n_samples,
+                                                  uint64_t seed, char *structures, float *energies) {
+    if (!c || W <= 0 || !seqs || !structures) return fail(ADX_EINVAL, "adx_sample_structures_batch: bad argument");
+    Problem &pb = c->pb;
+    std::vector<uint8_t> codes(size_t(W) * pb.Nraw);
+    for (size_t k = 0; k < codes.size(); k++) codes[k] = static_cast<uint8_t>(base_code(seqs[k]));
+    DevBuf<uint8_t> dseq;
+    HIP_TRY(dseq.upload(codes.data(), codes.size(), pb.stream));
+    return sample_structures(c, "adx_sample_structures_batch", dseq.p, W, variant, n_samples, seed, structures,
+                             energies);
+}
+
+extern "C" adx_status adx_walkers_sample_structures(adx_ctx *c, int variant, int n_samples, uint64_t seed,
+                                                    char *structures, float *energies) {
+    if (!c || !structures) return fail(ADX_EINVAL, "adx_walkers_sample_structures: null argument");
+    if (c->pb.mode == ADX_FOLD_PF && c->W <= 0)
+        return fail(ADX_ESTATE, "adx_walkers_sample_structures before adx_walkers_init");
+    return sample_structures(c, "adx_walkers_sample_structures", c->cur_seq.p, c->W, variant, n_samples, seed,
+                             structures, energies);
+}
+
+extern "C" adx_status adx_last_sample_ms(const adx_ctx *c, double *fill_ms, double *sample_ms) {
+    if (!c || !fill_ms || !sample_ms) return fail(ADX_EINVAL, "adx_last_sample_ms: null argument");
+    *fill_ms = c->pb.sample_fill_ms;
+    *sample_ms = c->pb.sample_draw_ms;
+    return ADX_OK;
 }
 
 extern "C" adx_status adx_score_batch(adx_ctx *c, int W, const char *seqs, double *scores,

@@ -66,6 +66,19 @@ int mfe_trace_chunk(const KArgs &ka, int W);    // sequences per launch, so the 
 hipError_t launch_mfe_trace(const KArgs &ka, int variant, const uint8_t *seqs, int W, int *scratch, int chunk,
                             char *structures, float *energies, hipStream_t stream);
 
+// ---- pf_sample.hip: structures drawn from the ensemble (FP64 fill of n sequences
+// from w0 into `scratch`, then one wave per sample: samples [k0, k0 + nk) of each,
+// structures[n][nk][variant length]; *flag is raised by a sample that met a loop bound)
+struct SamplePlan {
+    int seqs, samples;   // per launch, so that tables plus device-side output stay bounded
+};
+size_t pf_sample_slice_doubles(const KArgs &ka);   // doubles of HBM scratch per sequence
+SamplePlan pf_sample_plan(const KArgs &ka, int L, int W, int n_samples);
+hipError_t launch_pf_fill(const KArgs &ka, int variant, const uint8_t *seqs, int w0, int n, double *scratch,
+                          float *energies, hipStream_t stream);
+hipError_t launch_pf_sample(const KArgs &ka, int variant, const uint8_t *seqs, int w0, int n, double *scratch,
+                            int k0, int nk, uint64_t seed, char *structures, int *flag, hipStream_t stream);
+
 // ---- pf_cells.hip, pf_ring.hip
 size_t pf_cells_lds(const KArgs &ka);
 hipError_t launch_pf_cells(const KArgs &ka, const uint8_t *seqs, int W, const int *mask, float *gout,

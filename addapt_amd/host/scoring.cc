@@ -89,6 +89,24 @@ std::pair<string, double> GpuRnaFold::mfe_structure(string constraint) const {
     return {structure, double(e)};
 }
 
+// vrna_pbacktrack on the fold compound macrostate_prob builds
+std::pair<std::vector<string>, double> GpuRnaFold::sample_structures(int n, uint64_t seed, string constraint) const {
+    adx_fold *raw = nullptr;
+    gpu::check(adx_fold_create(gpu::params(), seq_.c_str(), 0, gpu_, &raw));
+    gpu::FoldPtr f(raw);
+    if (aptamer_)
+        gpu::check(adx_fold_add_motif(f.get(), aptamer_->seq().c_str(), aptamer_->fold().c_str(),
+                                      kT() * std::log(aptamer_->affinity() / 1e6)));
+    if (!constraint.empty()) gpu::check(adx_fold_add_constraint(f.get(), constraint.c_str()));
+    const size_t L = seq_.size();
+    string all(size_t(n > 0 ? n : 0) * L + 1, '\0');
+    float e = 0.f;
+    gpu::check(adx_fold_sample_structures(f.get(), n, seed, &all[0], &e));
+    std::vector<string> out;
+    for (int k = 0; k < n; k++) out.push_back(all.substr(size_t(k) * L, L));
+    return {out, double(e)};
+}
+
 // scoring.cc:37-51 (0-based, symmetric)
 double GpuRnaFold::base_pair_prob(int i, int j) const {
     const int n = static_cast<int>(seq_.size());

@@ -79,6 +79,8 @@ EXPORTS = [
     "adx_walkers_import", "adx_walkers_import_after", "adx_walkers_export_on", "adx_set_temperature", "adx_bppm_batch",
     "adx_walkers_rescore",
     "adx_fold_mfe_structure", "adx_mfe_structure_batch", "adx_walkers_mfe_structures",
+    "adx_fold_sample_structures", "adx_sample_structures_batch", "adx_walkers_sample_structures",
+    "adx_last_sample_ms",
 ]
 
 _lib = None
@@ -112,6 +114,12 @@ def lib():
         L.adx_mfe_structure_batch.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_int, C.c_char_p,
                                               C.POINTER(C.c_float)]
         L.adx_walkers_mfe_structures.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.POINTER(C.c_float)]
+        L.adx_fold_sample_structures.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_char_p, C.POINTER(C.c_float)]
+        L.adx_sample_structures_batch.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_uint64,
+                                                  C.c_char_p, C.POINTER(C.c_float)]
+        L.adx_walkers_sample_structures.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_char_p,
+                                                    C.POINTER(C.c_float)]
+        L.adx_last_sample_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.adx_fold_bpp.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double)]
         L.adx_fold_free.argtypes = [C.c_void_p]
         L.adx_ctx_create.argtypes = [C.POINTER(RunDesc), C.POINTER(C.c_void_p)]
@@ -217,6 +225,14 @@ class Fold:
         buf = C.create_string_buffer(self.N + 1)
         _check(lib().adx_fold_mfe_structure(self.ptr, buf, C.byref(g)))
         return g.value, buf.value.decode()
+
+    def sample_structures(self, n, seed=0):
+        """(ensemble energy kcal/mol, n dot-bracket strings drawn from the ensemble)."""
+        g = C.c_float()
+        buf = C.create_string_buffer(max(0, n) * self.N + 1)
+        _check(lib().adx_fold_sample_structures(self.ptr, n, seed, buf, C.byref(g)))
+        raw = buf.raw[:n * self.N].decode()
+        return g.value, [raw[k * self.N:(k + 1) * self.N] for k in range(n)]
 
     def bpp(self, i, j):
         p = C.c_double()
@@ -349,6 +365,35 @@ class Engine:
         """The same for the walkers' current sequences."""
         return self._structures(self.W, self._variant_length(variant), lambda st, e: lib().adx_walkers_mfe_structures(
             self.ptr, variant, st, e))
+
+    def _samples(self, W, L, n, call):
+        buf = C.create_string_buffer(W * max(0, n) * L + 1)
+        e = np.zeros(W, np.float32)
+        _check(call(buf, e.ctypes.data_as(C.POINTER(C.c_float))))
+        raw = buf.raw[:W * n * L].decode()
+        return [[raw[(w * n + k) * L:(w * n + k + 1) * L] for k in range(n)] for w in range(W)], e
+
+    def sample_structures(self, seqs, variant, n_samples, seed=0):
+        """(W lists of n_samples dot-bracket strings drawn from the ensembles of
+        `seqs` in fold variant `variant`, float32 ensemble energies); fold_mode="pf"
+        engines.  Sample k of sequence w depends on (seed, w, k) alone."""
+        W = len(seqs)
+        seqbuf = b"".join(_b(s) for s in seqs)
+        return self._samples(W, self._variant_length(variant), n_samples,
+                             lambda st, e: lib().adx_sample_structures_batch(self.ptr, W, seqbuf, variant, n_samples,
+                                                                             seed, st, e))
+
+    def walker_samples(self, variant, n_samples, seed=0):
+        """The same for the walkers' current sequences."""
+        return self._samples(self.W, self._variant_length(variant), n_samples,
+                             lambda st, e: lib().adx_walkers_sample_structures(self.ptr, variant, n_samples, seed,
+                                                                               st, e))
+
+    def last_sample_ms(self):
+        """(fill ms, sampling ms) of the last sample_structures / walker_samples call, from HIP events."""
+        a, b = C.c_double(), C.c_double()
+        _check(lib().adx_last_sample_ms(self.ptr, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def walkers_init(self, seeds, seqs=None):
         W = len(seeds)

@@ -9,6 +9,7 @@
 #include <map>
 #include <memory>
 #include <string>
+#include <cstdint>
 #include <utility>
 #include <vector>
 
@@ -54,6 +55,10 @@ public:
     /// kcal/mol, under an optional hard constraint; the aptamer motif counts as
     /// in macrostate_prob.  All '.' and +inf when the constraint admits nothing.
     std::pair<string, double> mfe_structure(string constraint = "") const;
+    /// n structures drawn from the Boltzmann ensemble (vrna_pbacktrack) under an
+    /// optional hard constraint, and the ensemble energy in kcal/mol; the aptamer
+    /// motif counts as in macrostate_prob.  Sample k under `seed` does not depend on n.
+    std::pair<std::vector<string>, double> sample_structures(int n, uint64_t seed, string constraint = "") const;
 
 private:
     string seq_;

@@ -90,6 +90,14 @@ adx_status adx_fold_mfe(adx_fold *f, float *energy_kcal);
  * ligand motif appears as the motif's own fold); all '.' and +inf when the
  * constraint admits no structure.  Filled and traced on the GPU. */
 adx_status adx_fold_mfe_structure(adx_fold *f, char *structure, float *energy_kcal);
+/* vrna_pbacktrack: n_samples structures drawn from the ensemble the compound
+ * describes (motif, constraint).  structures = n_samples * strlen(seq) chars,
+ * no terminators; energy_kcal optional (the ensemble energy, as adx_fold_pf).
+ * Sample k under `seed` does not depend on n_samples; a formed ligand motif
+ * appears as the motif's own fold; all '.' and +inf when the constraint
+ * admits no structure.  Filled (FP64) and sampled on the GPU. */
+adx_status adx_fold_sample_structures(adx_fold *f, int n_samples, uint64_t seed,
+                                      char *structures, float *energy_kcal);
 /* fc->exp_matrices->probs[fc->iindx[i] - j] with 1-based i < j (:47-50);
  * computed on first use with md.compute_bpp (:41-44). */
 adx_status adx_fold_bpp(adx_fold *f, int i, int j, double *prob);
@@ -288,6 +296,24 @@ adx_status adx_mfe_structure_batch(adx_ctx *ctx, int n_walkers, const char *seqs
 /* The same for the walkers' current sequences, read on the device
  * (ADX_ESTATE before adx_walkers_init). */
 adx_status adx_walkers_mfe_structures(adx_ctx *ctx, int variant, char *structures, float *energies);
+
+/* W sequences, variant v of a PF context: structures = W * n_samples * L chars
+ * (sequence-major, then sample; L = the variant's folded, context-padded
+ * length), energies[W] optional (the variant's ensemble energies, an FP64
+ * fill independent of adx_score_batch's dG).  Sample k of sequence w under
+ * `seed` depends on nothing else.  ADX_FOLD_PF contexts only
+ * (ADX_EUNSUPPORTED on an MFE context).  Touches no walker state. */
+adx_status adx_sample_structures_batch(adx_ctx *ctx, int n_walkers, const char *seqs, int variant,
+                                       int n_samples, uint64_t seed, char *structures, float *energies);
+
+/* The same for the walkers' current sequences, read on the device; w = walker
+ * index (ADX_ESTATE before adx_walkers_init). */
+adx_status adx_walkers_sample_structures(adx_ctx *ctx, int variant, int n_samples, uint64_t seed,
+                                         char *structures, float *energies);
+
+/* Device time (ms, HIP events) of the context's last sampling call: the FP64
+ * fill and the sampling kernel. */
+adx_status adx_last_sample_ms(const adx_ctx *ctx, double *fill_ms, double *sample_ms);
 
 /* Variant v of the score: which (context, condition, macrostate or -1). */
 adx_status adx_variant_desc(const adx_ctx *ctx, int v, int *context, int *condition,
