@@ -146,6 +146,19 @@ __device__ __forceinline__ bool allowed(const LT &L, int i, int j) {
     return L.enc[i] == L.enc[j];
 }
 
+// The band of a refold after positions m_lo .. m_hi changed: rows clo .. chi of
+// span dd hold the cells of qbm / qm1 that contain a changed position (or the
+// neighbour whose dangle they read), rows qlo .. qhi of span s the cells of qm
+// that do.  A fold from scratch: every row
+struct Band {
+    bool incr;
+    int N, m_lo, m_hi;
+    __device__ __forceinline__ int clo(int dd) const { return incr ? max(1, m_lo - 1 - dd) : 1; }
+    __device__ __forceinline__ int chi(int dd) const { return incr ? min(N - dd, m_hi + 1) : N - dd; }
+    __device__ __forceinline__ int qlo(int s) const { return incr ? max(1, m_lo - 2 - s) : 1; }
+    __device__ __forceinline__ int qhi(int s) const { return incr ? min(N - s, m_hi + 2) : N - s; }
+};
+
 // interior-loop shape kinds (dev_types.hpp TermKind; -1 = generic)
 __host__ __device__ constexpr int loop_kind(int n1, int n2) {
     return (n1 == 0 && n2 == 0) ? TK_STK

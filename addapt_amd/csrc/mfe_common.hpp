@@ -242,19 +242,6 @@ __device__ __forceinline__ void carve_bytes(LT &l, uint8_t *y, int NP) {
     l.raw = y + 7 * NP;
 }
 
-// The band of a refold after positions m_lo .. m_hi changed: rows clo .. chi of
-// span dd hold the cells of qbm / qm1 that contain a changed position (or the
-// neighbour whose dangle they read), rows qlo .. qhi of span s the cells of qm
-// that do.  A fold from scratch: every row
-struct Band {
-    bool incr;
-    int N, m_lo, m_hi;
-    __device__ __forceinline__ int clo(int dd) const { return incr ? max(1, m_lo - 1 - dd) : 1; }
-    __device__ __forceinline__ int chi(int dd) const { return incr ? min(N - dd, m_hi + 1) : N - dd; }
-    __device__ __forceinline__ int qlo(int s) const { return incr ? max(1, m_lo - 2 - s) : 1; }
-    __device__ __forceinline__ int qhi(int s) const { return incr ? min(N - s, m_hi + 2) : N - s; }
-};
-
 // A fold's incremental state (KArgs::tab): the slot it writes and, for a
 // refold, the slot it restores and the changed positions in the folded sequence
 struct IncM {

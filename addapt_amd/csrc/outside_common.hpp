@@ -119,7 +119,7 @@ struct OxSize {
 };
 
 // Loop size U >= 6 over the four lanes of an inner cell (phase r = lane & 3),
-// as pf_cells.hip PxSizeQ: lane r takes one special shape -- the bulges (0,U)
+// as pf_common.hpp PSizeQ: lane r takes one special shape -- the bulges (0,U)
 // (U,0) and 1 x n loops (1,U-1) (U-1,1), a window read, an outer-code read and
 // a factor gather -- and the generic shapes n1 = 2 + r + 4m <= U - 2 (one
 // window read at a per-lane base + immediate offset, its factor in a VGPR; 0

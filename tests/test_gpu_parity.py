@@ -58,6 +58,39 @@ def test_fold_layer_matches_oracle(native, oracle):
             assert abs(g - ref) <= DG_TOL, (seq, cst, g, float(ref))
 
 
+def _mid_pair(n):
+    """An enforced pair of span 5 in the middle, the rest free."""
+    a = n // 2 - 2
+    return "." * (a - 1) + "(....)" + "." * (n - a - 5)
+
+
+def _mid_run(n, ch, k=10):
+    """Constraint character ch on k positions in the middle, the rest free."""
+    a = (n - k) // 2
+    return "." * a + ch * k + "." * (n - a - k)
+
+
+@pytest.mark.parametrize("seq,cst", [("GUGC" * 18, None), ("GUGC" * 25, None), ("GUGC" * 18, _mid_run(72, "x")),
+                                     ("GUGC" * 25, _mid_pair(100))],
+                         ids=["n72", "n100", "n72-x", "n100-pair"])
+def test_fold_layer_dense_diagonals(native, oracle, seq, cst):
+    """G on every odd position, U or C on every even one: every cell of every
+    odd diagonal is pairable, so D = 7, the first diagonal with B records, holds
+    65 of them at 72 nt: one cell in pf_cells_kernel's second lane-set (100 nt: the
+    last length).  'x' on ten middle positions forbids their pairs and leaves
+    the unpaired runs up / dn whole: the unmasked shapes with `constrained` set.
+    The enforced pair cuts the runs, so the cells around it get the record's
+    masked bit and their B batches take the masked (MK) shapes, on diagonals
+    that keep more than 64 records (100 nt: D = 7 has 81 pairable cells, one
+    masked; D = 9 has 79, three masked)."""
+    f = native.Fold(seq)
+    if cst:
+        f.add_constraint(cst)
+    g = f.pf()
+    ref = np.float32(oracle.pf_energy(seq, cst))
+    assert abs(g - ref) <= DG_TOL, (seq, cst, g, float(ref))
+
+
 def test_fold_layer_motif(native, oracle):
     apt, fold = workloads.THEO_SEQ, workloads.THEO_FOLD
     e = oracle.theo_bonus()

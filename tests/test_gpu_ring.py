@@ -69,6 +69,39 @@ def test_ring_fold_layer(native, oracle):
         assert abs(g - np.float32(ref)) <= DG_TOL, (n, g, ref)
 
 
+def _mid_pair(n):
+    """An enforced pair of span 5 in the middle, the rest free."""
+    a = n // 2 - 2
+    return "." * (a - 1) + "(....)" + "." * (n - a - 5)
+
+
+def _mid_run(n, ch, k=10):
+    """Constraint character ch on k positions in the middle, the rest free."""
+    a = (n - k) // 2
+    return "." * a + ch * k + "." * (n - a - k)
+
+
+@pytest.mark.parametrize("seq,cst", [("GUGC" * 34, None), ("GUGC" * 37 + "GU", None), ("GUGC" * 34, _mid_run(136, "x")),
+                                     ("GUGC" * 37 + "GU", _mid_pair(150))],
+                         ids=["n136", "n150", "n136-x", "n150-pair"])
+def test_ring_fold_layer_dense_diagonals(native, oracle, seq, cst):
+    """G on every odd position, U or C on every even one: every cell of every
+    odd diagonal is pairable, so D = 7, the first diagonal with B records, holds
+    129 of them at 136 nt: one cell in pf_ring_kernel's third lane-set (150 nt: the
+    last length).  'x' on ten middle positions forbids their pairs and leaves
+    the unpaired runs up / dn whole: the unmasked shapes with `constrained` set.
+    The enforced pair cuts the runs, so the cells around it get the record's
+    masked bit and their B batches take the masked (MK) shapes, on diagonals
+    that keep more than 128 records (150 nt: D = 7 has 131 pairable cells, one
+    masked; D = 9 has 129, three masked)."""
+    f = native.Fold(seq)
+    if cst:
+        f.add_constraint(cst)
+    g = f.pf()
+    ref = np.float32(oracle.pf_energy(seq, cst))
+    assert abs(g - ref) <= DG_TOL, (seq, cst, g, float(ref))
+
+
 @pytest.mark.parametrize("N", [101, 150])
 def test_ring_score_batch(native, oracle, N):
     tmpl, active = workloads.synthetic(N)

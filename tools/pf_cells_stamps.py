@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Per-wave phase breakdown of pf_cells_kernel (diagnostic stamp build:
 ADX_LIB=addapt_amd/_lib/ablate/lib_stamp.so).  Runs PF MC steps (N=100 bench
-objective; "tables" = the barrier + block_or after s.prolog, s.loads, s.rissue).  Waves 0-7 = B (interior loops), 8-9 M, 10-11 F, 12 Q, 13 records.
+objective; "tables" = the barrier + block_or after s.prolog, s.loads, s.rissue).  Waves 0-7 = B (interior loops), 8 F, 9 Q, 10 records, 11-14 M.
+"Bshape" ends after the quad sum and the partial's store (pf_common.hpp pb_batch, as
+the ring's slot); in profiles/ records from before pf_common.hpp it ended before them
+and "Bwrite" held that time, so compare Bshape + Bwrite across the two.
 usage: pf_cells_stamps.py [N] [W] [steps]"""
 import ctypes as C
 import os
