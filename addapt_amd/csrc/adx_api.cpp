@@ -429,6 +429,7 @@ struct Problem {
     DevBuf<int> dTrace;          // c / fm / fm1 scratch of mfe_trace_kernel, one launch chunk
     DevBuf<double> dSample;      // qb / qm / qm1 / q5 scratch of pf_fill_kernel, one launch chunk
     float sample_fill_ms = 0.f, sample_draw_ms = 0.f;   // the last sample() call, from HIP events
+    float ens_bppm_ms = 0.f, ens_struct_ms = 0.f;       // the last ensemble() call, from HIP events
     size_t tab_slot = 0;
     bool state_on = false;   // set for MC launches only (not for adx_score_batch)
     std::unique_ptr<DevTables> hT;
@@ -737,6 +738,77 @@ struct Problem {
         return ADX_OK;
     }
 
+    // Centroid and MEA structures of W sequences (device codes) for the unconstrained
+    // variant v, to HOST buffers: centroid, mea = W * variants[v].N chars, stats[W]
+    // (each optional), probs = the W matrices (optional).  Per launch chunk the
+    // outside pass writes the matrices to a device buffer and ensemble_struct_kernel
+    // reads them there.  Every buffer is the call's own: no fold state is touched.
+    // chunk > 0 overrides the sequences per launch (the results do not depend on it).
+    adx_status ensemble(const uint8_t *dseqs, int W, int v, double gamma, char *centroid, char *mea,
+                        adx_ensemble_stats *stats, double *probs, int chunk = 0) {
+        static_assert(sizeof(adx_ensemble_stats) == 3 * sizeof(double), "the kernel writes three doubles per sequence");
+        const size_t L = size_t(variants[v].N);
+        DevBuf<int> dbv;
+        HIP_TRY(dbv.upload(&v, 1, stream));
+        KArgs ka = kargs();
+        ka.bvars = dbv.p;
+        ka.n_bvars = 1;
+        ka.bvar_slot = nullptr;   // no stored tables are reused here
+        ka.n_pairs = 0;
+        ka.pairs = nullptr;
+        ka.pair_p = nullptr;
+        if (bppm_lds_bytes(ka, nullptr) == 0)
+            return fail(ADX_EUNSUPPORTED, "base-pair probabilities of length %d do not fit one CU's LDS yet", Nmax);
+        int per = ensemble_struct_chunk(int(L), W);
+        if (chunk > 0) per = std::min(per, chunk);
+        const size_t slice = ensemble_struct_slice_doubles(int(L));
+        DevBuf<char> dscr, dcen, dmea;
+        DevBuf<double> dfull, dtab, dst;
+        const size_t scr = bppm_scratch_bytes(ka, per);
+        if (scr) HIP_TRY(dscr.alloc(scr));
+        ka.bppm_scratch = dscr.p;
+        HIP_TRY(dfull.alloc(size_t(per) * L * L));
+        HIP_TRY(dtab.alloc(size_t(per) * slice));
+        HIP_TRY(dcen.alloc(size_t(per) * L));
+        HIP_TRY(dmea.alloc(size_t(per) * L));
+        HIP_TRY(dst.alloc(size_t(per) * 3));
+        hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+        struct Drop {
+            hipEvent_t *ev;
+            ~Drop() {
+                for (int k = 0; k < 3; k++)
+                    if (ev[k]) (void)hipEventDestroy(ev[k]);
+            }
+        } drop{ev};
+        for (auto &e : ev) HIP_TRY(hipEventCreate(&e));
+        ens_bppm_ms = ens_struct_ms = 0.f;
+        for (int w0 = 0; w0 < W; w0 += per) {
+            const int n = std::min(per, W - w0);
+            HIP_TRY(hipMemsetAsync(dfull.p, 0, sizeof(double) * n * L * L, stream));   // the outside pass writes pairs only
+            HIP_TRY(hipEventRecord(ev[0], stream));
+            HIP_TRY(launch_bppm(ka, dseqs + size_t(w0) * Nraw, n, nullptr, dfull.p, int(L), nullptr, ka.bppm_scratch,
+                                stream));
+            HIP_TRY(hipEventRecord(ev[1], stream));
+            HIP_TRY(launch_ensemble_struct(dfull.p, int(L), n, gamma, dtab.p, dcen.p, dmea.p, dst.p, stream));
+            HIP_TRY(hipEventRecord(ev[2], stream));
+            if (centroid)
+                HIP_TRY(hipMemcpyAsync(centroid + size_t(w0) * L, dcen.p, size_t(n) * L, hipMemcpyDeviceToHost, stream));
+            if (mea) HIP_TRY(hipMemcpyAsync(mea + size_t(w0) * L, dmea.p, size_t(n) * L, hipMemcpyDeviceToHost, stream));
+            if (stats)
+                HIP_TRY(hipMemcpyAsync(stats + w0, dst.p, sizeof(adx_ensemble_stats) * n, hipMemcpyDeviceToHost, stream));
+            if (probs)
+                HIP_TRY(hipMemcpyAsync(probs + size_t(w0) * L * L, dfull.p, sizeof(double) * n * L * L,
+                                       hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipStreamSynchronize(stream));   // the buffers are reused by the next chunk
+            float a = 0.f, b = 0.f;
+            HIP_TRY(hipEventElapsedTime(&a, ev[0], ev[1]));
+            HIP_TRY(hipEventElapsedTime(&b, ev[1], ev[2]));
+            ens_bppm_ms += a;
+            ens_struct_ms += b;
+        }
+        return ADX_OK;
+    }
+
     // the per-walker buffers a fold of W walkers writes (grow-only)
     adx_status prepare(int W) {
         adx_status so = ensure_ovf(W);
@@ -869,14 +941,14 @@ static adx_status fold_problem(adx_fold *f, int mode, Problem &pb) {
     return pb.upload_all();
 }
 
-// One fold of the compound f in mode 0 (partition function) or 1 (MFE).
-static adx_status fold_energy(adx_fold *f, int mode, float *energy, std::vector<double> *bpp = nullptr) {
-    Problem pb;
+// One fold of the compound f in mode 0 (partition function, on a calibrated
+// scale) or 1 (MFE): pb is left uploaded and dseq holds the sequence, for an
+// outside pass to follow.
+static adx_status fold_one(adx_fold *f, int mode, Problem &pb, DevBuf<uint8_t> &dseq, float *energy) {
     adx_status s = fold_problem(f, mode, pb);
     if (s) return s;
     const int N = static_cast<int>(f->seq.size());
     std::vector<uint8_t> codes = encode(f->seq);
-    DevBuf<uint8_t> dseq;
     DevBuf<double> dsc;
     DevBuf<float> ddg;
     HIP_TRY(dseq.upload(codes.data(), codes.size(), pb.stream));
@@ -911,23 +983,40 @@ static adx_status fold_energy(adx_fold *f, int mode, float *energy, std::vector<
         if (s) return s;
     }
     *energy = g;
-    if (bpp) {   // outside pass on the calibrated scale
-        bpp->assign(size_t(N) * N, 0.0);
-        if (!std::isfinite(g)) return ADX_OK;   // empty ensemble: every probability is 0
-        pb.bvars.assign(1, 0);
-        HIP_TRY(pb.dBvars.upload(pb.bvars.data(), 1, pb.stream));
-        if (bppm_lds_bytes(pb.kargs(), nullptr) == 0)
-            return fail(ADX_EUNSUPPORTED, "base-pair probabilities of length %d do not fit one CU's LDS yet", N);
-        s = pb.ensure_scratch(pb.kargs(), 1);
-        if (s) return s;
-        const KArgs ka = pb.kargs();
-        DevBuf<double> dfull;
-        HIP_TRY(dfull.alloc(size_t(N) * N));
-        HIP_TRY(hipMemsetAsync(dfull.p, 0, sizeof(double) * N * N, pb.stream));
-        HIP_TRY(launch_bppm(ka, dseq.p, 1, nullptr, dfull.p, N, nullptr, ka.bppm_scratch, pb.stream));
-        HIP_TRY(hipMemcpyAsync(bpp->data(), dfull.p, sizeof(double) * N * N, hipMemcpyDeviceToHost, pb.stream));
-        HIP_TRY(hipStreamSynchronize(pb.stream));
-    }
+    return ADX_OK;
+}
+
+// The outside pass of a fold_one(mode 0) problem whose energy is finite: the
+// N x N pair probabilities into dfull, which stays on the device (queued on
+// pb.stream, not awaited).
+static adx_status fold_outside(Problem &pb, const DevBuf<uint8_t> &dseq, int N, DevBuf<double> &dfull) {
+    pb.bvars.assign(1, 0);
+    HIP_TRY(pb.dBvars.upload(pb.bvars.data(), 1, pb.stream));
+    if (bppm_lds_bytes(pb.kargs(), nullptr) == 0)
+        return fail(ADX_EUNSUPPORTED, "base-pair probabilities of length %d do not fit one CU's LDS yet", N);
+    adx_status s = pb.ensure_scratch(pb.kargs(), 1);
+    if (s) return s;
+    const KArgs ka = pb.kargs();
+    HIP_TRY(dfull.alloc(size_t(N) * N));
+    HIP_TRY(hipMemsetAsync(dfull.p, 0, sizeof(double) * N * N, pb.stream));
+    HIP_TRY(launch_bppm(ka, dseq.p, 1, nullptr, dfull.p, N, nullptr, ka.bppm_scratch, pb.stream));
+    return ADX_OK;
+}
+
+// The compound's energy in mode 0 or 1 and, in mode 0, optionally its pair probabilities.
+static adx_status fold_energy(adx_fold *f, int mode, float *energy, std::vector<double> *bpp = nullptr) {
+    Problem pb;
+    DevBuf<uint8_t> dseq;
+    adx_status s = fold_one(f, mode, pb, dseq, energy);
+    if (s || mode == 1 || !bpp) return s;
+    const int N = static_cast<int>(f->seq.size());
+    bpp->assign(size_t(N) * N, 0.0);
+    if (!std::isfinite(*energy)) return ADX_OK;   // empty ensemble: every probability is 0
+    DevBuf<double> dfull;
+    s = fold_outside(pb, dseq, N, dfull);   // on the calibrated scale
+    if (s) return s;
+    HIP_TRY(hipMemcpyAsync(bpp->data(), dfull.p, sizeof(double) * N * N, hipMemcpyDeviceToHost, pb.stream));
+    HIP_TRY(hipStreamSynchronize(pb.stream));
     return ADX_OK;
 }
 
@@ -991,6 +1080,67 @@ extern "C" adx_status adx_fold_bpp(adx_fold *f, int i, int j, double *prob) {
         }
     }
     *prob = (i != j) ? f->bpp[size_t(i - 1) * N + (j - 1)] : 0.0;
+    return ADX_OK;
+}
+
+static bool ensemble_args_ok(double gamma, const char *centroid, const char *mea, const adx_ensemble_stats *stats) {
+    return std::isfinite(gamma) && gamma > 0.0 && (centroid || mea || stats);
+}
+
+extern "C" adx_status adx_fold_ensemble_structures(adx_fold *f, double gamma, char *centroid, char *mea,
+                                                   adx_ensemble_stats *stats) {
+    if (!f) return fail(ADX_EINVAL, "adx_fold_ensemble_structures: null argument");
+    if (!ensemble_args_ok(gamma, centroid, mea, stats))
+        return fail(ADX_EINVAL, "adx_fold_ensemble_structures: gamma %g not finite and > 0, or nothing to return", gamma);
+    Problem pb;
+    DevBuf<uint8_t> dseq;
+    DevBuf<double> dfull, dtab, dst;
+    DevBuf<char> dcen, dmea;
+    const size_t N = f->seq.size();
+    bool empty;
+    adx_status s;
+    if (N < 5) {
+        // no pair closes a hairpin of 3 in fewer than 5 bases: the ensemble is the open
+        // chain (every probability 0), or nothing when the constraint demands a pair.
+        // The fold kernels are not run.
+        pb.device = f->device;
+        s = pb.init_device();
+        if (s) return s;
+        empty = f->constraint.find_first_of("()|<>") != std::string::npos;
+    } else {
+        float g = NAN;
+        s = fold_one(f, 0, pb, dseq, &g);
+        if (s) return s;
+        empty = !std::isfinite(g);
+    }
+    if (centroid) centroid[N] = 0;
+    if (mea) mea[N] = 0;
+    std::vector<double> bpp(N * N, 0.0);   // becomes the probabilities adx_fold_bpp serves, as a by-product
+    if (empty) {                           // every probability is 0 and there is nothing to summarise
+        f->bpp.swap(bpp);
+        if (centroid) std::memset(centroid, '.', N);
+        if (mea) std::memset(mea, '.', N);
+        if (stats) stats->mea = stats->centroid_dist = stats->diversity = NAN;
+        return ADX_OK;
+    }
+    if (N < 5) {
+        HIP_TRY(dfull.alloc(N * N));
+        HIP_TRY(hipMemsetAsync(dfull.p, 0, sizeof(double) * N * N, pb.stream));
+    } else {
+        s = fold_outside(pb, dseq, int(N), dfull);
+        if (s) return s;
+    }
+    HIP_TRY(dtab.alloc(ensemble_struct_slice_doubles(int(N))));
+    HIP_TRY(dcen.alloc(N));
+    HIP_TRY(dmea.alloc(N));
+    HIP_TRY(dst.alloc(3));
+    HIP_TRY(launch_ensemble_struct(dfull.p, int(N), 1, gamma, dtab.p, dcen.p, dmea.p, dst.p, pb.stream));
+    if (centroid) HIP_TRY(hipMemcpyAsync(centroid, dcen.p, N, hipMemcpyDeviceToHost, pb.stream));
+    if (mea) HIP_TRY(hipMemcpyAsync(mea, dmea.p, N, hipMemcpyDeviceToHost, pb.stream));
+    if (stats) HIP_TRY(hipMemcpyAsync(stats, dst.p, sizeof(*stats), hipMemcpyDeviceToHost, pb.stream));
+    HIP_TRY(hipMemcpyAsync(bpp.data(), dfull.p, sizeof(double) * N * N, hipMemcpyDeviceToHost, pb.stream));
+    HIP_TRY(hipStreamSynchronize(pb.stream));
+    f->bpp.swap(bpp);
     return ADX_OK;
 }
 
@@ -1624,16 +1774,23 @@ extern "C" adx_status adx_set_temperature(adx_ctx *c, double t) {
     return ADX_OK;
 }
 
-extern "C" adx_status adx_bppm_batch(adx_ctx *c, int W, const char *seqs, int condition, int context,
-                                      double *probs) {
-    if (!c || W <= 0 || !seqs || !probs) return fail(ADX_EINVAL, "adx_bppm_batch: bad argument");
-    Problem &pb = c->pb;
-    if (pb.mode != ADX_FOLD_PF) return fail(ADX_EUNSUPPORTED, "adx_bppm_batch: partition-function contexts only");
+// the variant that folds (context, condition) without a constraint, or -1
+static int free_fold_variant(const adx_ctx *c, int condition, int context) {
+    const Problem &pb = c->pb;
     const int want_ctx = c->n_contexts > 0 ? context : -1;
     int v = -1;
     for (size_t k = 0; k < pb.variants.size(); k++)
         if (pb.variants[k].ctx == want_ctx && pb.vmac[k] == -1 && pb.variants[k].motif == (condition == ADX_HOLO ? 1 : 0))
             v = static_cast<int>(k);
+    return v;
+}
+
+extern "C" adx_status adx_bppm_batch(adx_ctx *c, int W, const char *seqs, int condition, int context,
+                                      double *probs) {
+    if (!c || W <= 0 || !seqs || !probs) return fail(ADX_EINVAL, "adx_bppm_batch: bad argument");
+    Problem &pb = c->pb;
+    if (pb.mode != ADX_FOLD_PF) return fail(ADX_EUNSUPPORTED, "adx_bppm_batch: partition-function contexts only");
+    const int v = free_fold_variant(c, condition, context);
     if (v < 0) return fail(ADX_EINVAL, "adx_bppm_batch: the objective has no (context %d, condition %d) fold", context, condition);
     const int N = pb.Nraw, L = pb.variants[v].N;
     std::vector<uint8_t> codes(size_t(W) * N);
@@ -1745,6 +1902,49 @@ extern "C" adx_status adx_last_sample_ms(const adx_ctx *c, double *fill_ms, doub
     if (!c || !fill_ms || !sample_ms) return fail(ADX_EINVAL, "adx_last_sample_ms: null argument");
     *fill_ms = c->pb.sample_fill_ms;
     *sample_ms = c->pb.sample_draw_ms;
+    return ADX_OK;
+}
+
+// centroid and MEA structures of W device sequences for the (context, condition) unconstrained fold
+static adx_status ensemble_structures(adx_ctx *c, const char *who, const uint8_t *dseqs, int W, int condition,
+                                      int context, double gamma, char *centroid, char *mea,
+                                      adx_ensemble_stats *stats, double *probs) {
+    Problem &pb = c->pb;
+    if (!ensemble_args_ok(gamma, centroid, mea, stats))
+        return fail(ADX_EINVAL, "%s: gamma %g not finite and > 0, or nothing to return", who, gamma);
+    if (pb.mode != ADX_FOLD_PF) return fail(ADX_EUNSUPPORTED, "%s: partition-function contexts only", who);
+    const int v = free_fold_variant(c, condition, context);
+    if (v < 0) return fail(ADX_EINVAL, "%s: the objective has no (context %d, condition %d) fold", who, context, condition);
+    return pb.ensemble(dseqs, W, v, gamma, centroid, mea, stats, probs);
+}
+
+extern "C" adx_status adx_ensemble_structures_batch(adx_ctx *c, int W, const char *seqs, int condition, int context,
+                                                    double gamma, char *centroid, char *mea,
+                                                    adx_ensemble_stats *stats, double *probs) {
+    if (!c || W <= 0 || !seqs) return fail(ADX_EINVAL, "adx_ensemble_structures_batch: bad argument");
+    Problem &pb = c->pb;
+    std::vector<uint8_t> codes(size_t(W) * pb.Nraw);
+    for (size_t k = 0; k < codes.size(); k++) codes[k] = static_cast<uint8_t>(base_code(seqs[k]));
+    DevBuf<uint8_t> dseq;
+    HIP_TRY(dseq.upload(codes.data(), codes.size(), pb.stream));
+    return ensemble_structures(c, "adx_ensemble_structures_batch", dseq.p, W, condition, context, gamma, centroid, mea,
+                               stats, probs);
+}
+
+extern "C" adx_status adx_walkers_ensemble_structures(adx_ctx *c, int condition, int context, double gamma,
+                                                      char *centroid, char *mea, adx_ensemble_stats *stats,
+                                                      double *probs) {
+    if (!c) return fail(ADX_EINVAL, "adx_walkers_ensemble_structures: null context");
+    if (c->pb.mode == ADX_FOLD_PF && c->W <= 0)
+        return fail(ADX_ESTATE, "adx_walkers_ensemble_structures before adx_walkers_init");
+    return ensemble_structures(c, "adx_walkers_ensemble_structures", c->cur_seq.p, c->W, condition, context, gamma,
+                               centroid, mea, stats, probs);
+}
+
+extern "C" adx_status adx_last_ensemble_ms(const adx_ctx *c, double *bppm_ms, double *struct_ms) {
+    if (!c || !bppm_ms || !struct_ms) return fail(ADX_EINVAL, "adx_last_ensemble_ms: null argument");
+    *bppm_ms = c->pb.ens_bppm_ms;
+    *struct_ms = c->pb.ens_struct_ms;
     return ADX_OK;
 }
 

@@ -79,6 +79,14 @@ hipError_t launch_pf_fill(const KArgs &ka, int variant, const uint8_t *seqs, int
 hipError_t launch_pf_sample(const KArgs &ka, int variant, const uint8_t *seqs, int w0, int n, double *scratch,
                             int k0, int nk, uint64_t seed, char *structures, int *flag, hipStream_t stream);
 
+// ---- ensemble_struct.hip: centroid and MEA structures of n sequences from their
+// pair-probability matrices probs[n][L][L] (launch_bppm's `full`, ld = L):
+// centroid, mea = n * L chars, stats = n * 3 doubles (mea, centroid_dist, diversity)
+size_t ensemble_struct_slice_doubles(int L);   // doubles of HBM scratch per sequence (M and w)
+int ensemble_struct_chunk(int L, int W);       // sequences per launch: matrices + slices stay bounded
+hipError_t launch_ensemble_struct(const double *probs, int L, int n, double gamma, double *scratch, char *centroid,
+                                  char *mea, double *stats, hipStream_t stream);
+
 // ---- pf_cells.hip, pf_ring.hip
 size_t pf_cells_lds(const KArgs &ka);
 hipError_t launch_pf_cells(const KArgs &ka, const uint8_t *seqs, int W, const int *mask, float *gout,

@@ -107,6 +107,23 @@ std::pair<std::vector<string>, double> GpuRnaFold::sample_structures(int n, uint
     return {out, double(e)};
 }
 
+// RNAfold -p --MEA on the fold compound macrostate_prob builds
+EnsembleStructures GpuRnaFold::ensemble_structures(double gamma, string constraint) const {
+    adx_fold *raw = nullptr;
+    gpu::check(adx_fold_create(gpu::params(), seq_.c_str(), 0, gpu_, &raw));
+    gpu::FoldPtr f(raw);
+    if (aptamer_)
+        gpu::check(adx_fold_add_motif(f.get(), aptamer_->seq().c_str(), aptamer_->fold().c_str(),
+                                      kT() * std::log(aptamer_->affinity() / 1e6)));
+    if (!constraint.empty()) gpu::check(adx_fold_add_constraint(f.get(), constraint.c_str()));
+    string centroid(seq_.size() + 1, '\0'), mea(seq_.size() + 1, '\0');
+    adx_ensemble_stats st;
+    gpu::check(adx_fold_ensemble_structures(f.get(), gamma, &centroid[0], &mea[0], &st));
+    centroid.resize(seq_.size());
+    mea.resize(seq_.size());
+    return {centroid, mea, st.mea, st.centroid_dist, st.diversity};
+}
+
 // scoring.cc:37-51 (0-based, symmetric)
 double GpuRnaFold::base_pair_prob(int i, int j) const {
     const int n = static_cast<int>(seq_.size());

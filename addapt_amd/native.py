@@ -60,6 +60,10 @@ class Info(C.Structure):
                 ("n_mutable", C.c_int), ("max_walkers", C.c_int), ("scale_per_nt", C.c_double)]
 
 
+class EnsembleStats(C.Structure):
+    _fields_ = [("mea", C.c_double), ("centroid_dist", C.c_double), ("diversity", C.c_double)]
+
+
 class Trace(C.Structure):
     _fields_ = [("position", C.POINTER(C.c_int32)), ("base", C.c_char_p),
                 ("outcome", C.POINTER(C.c_int32)), ("temperature", C.POINTER(C.c_double)),
@@ -81,6 +85,8 @@ EXPORTS = [
     "adx_fold_mfe_structure", "adx_mfe_structure_batch", "adx_walkers_mfe_structures",
     "adx_fold_sample_structures", "adx_sample_structures_batch", "adx_walkers_sample_structures",
     "adx_last_sample_ms",
+    "adx_fold_ensemble_structures", "adx_ensemble_structures_batch", "adx_walkers_ensemble_structures",
+    "adx_last_ensemble_ms",
 ]
 
 _lib = None
@@ -120,6 +126,14 @@ def lib():
         L.adx_walkers_sample_structures.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_char_p,
                                                     C.POINTER(C.c_float)]
         L.adx_last_sample_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.adx_fold_ensemble_structures.argtypes = [C.c_void_p, C.c_double, C.c_char_p, C.c_char_p,
+                                                   C.POINTER(EnsembleStats)]
+        L.adx_ensemble_structures_batch.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_double,
+                                                    C.c_char_p, C.c_char_p, C.POINTER(EnsembleStats),
+                                                    C.POINTER(C.c_double)]
+        L.adx_walkers_ensemble_structures.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_char_p, C.c_char_p,
+                                                      C.POINTER(EnsembleStats), C.POINTER(C.c_double)]
+        L.adx_last_ensemble_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.adx_fold_bpp.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double)]
         L.adx_fold_free.argtypes = [C.c_void_p]
         L.adx_ctx_create.argtypes = [C.POINTER(RunDesc), C.POINTER(C.c_void_p)]
@@ -233,6 +247,14 @@ class Fold:
         _check(lib().adx_fold_sample_structures(self.ptr, n, seed, buf, C.byref(g)))
         raw = buf.raw[:n * self.N].decode()
         return g.value, [raw[k * self.N:(k + 1) * self.N] for k in range(n)]
+
+    def ensemble_structures(self, gamma=1.0):
+        """(centroid, MEA structure, EnsembleStats) of the ensemble: RNAfold -p --MEA's
+        lines after the MFE one.  The statistics are NaN when the constraint admits nothing."""
+        cen, mea = C.create_string_buffer(self.N + 1), C.create_string_buffer(self.N + 1)
+        st = EnsembleStats()
+        _check(lib().adx_fold_ensemble_structures(self.ptr, gamma, cen, mea, C.byref(st)))
+        return cen.value.decode(), mea.value.decode(), st
 
     def bpp(self, i, j):
         p = C.c_double()
@@ -393,6 +415,43 @@ class Engine:
         """(fill ms, sampling ms) of the last sample_structures / walker_samples call, from HIP events."""
         a, b = C.c_double(), C.c_double()
         _check(lib().adx_last_sample_ms(self.ptr, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def _ensemble(self, W, condition, context, with_probs, call):
+        L = self.N + (sum(self._ctx_lens[context]) if self._ctx_lens and 0 <= context < len(self._ctx_lens) else 0)
+        cen, mea = C.create_string_buffer(W * L + 1), C.create_string_buffer(W * L + 1)
+        st = np.zeros((W, 3), np.float64)
+        P = np.zeros(W * L * L if with_probs else 0, np.float64)
+        c = HOLO if condition in ("holo", HOLO) else APO
+        _check(call(c, cen, mea, st.ctypes.data_as(C.POINTER(EnsembleStats)),
+                    P.ctypes.data_as(C.POINTER(C.c_double)) if with_probs else None))
+        cen, mea = cen.raw[:W * L].decode(), mea.raw[:W * L].decode()
+        out = ([cen[w * L:(w + 1) * L] for w in range(W)], [mea[w * L:(w + 1) * L] for w in range(W)], st)
+        return out + (P.reshape(W, L, L),) if with_probs else out
+
+    def ensemble_structures(self, seqs, condition="apo", context=0, gamma=1.0, with_probs=False):
+        """(centroids, MEA structures, stats) of `seqs` in the unconstrained
+        (context, condition) fold, as bppm_batch addresses it: W dot-bracket strings
+        each and a (W, 3) float64 array of (mea, centroid_dist, diversity).
+        with_probs appends the (W, L, L) matrices the structures were computed from.
+        fold_mode="pf" engines."""
+        W = len(seqs)
+        seqbuf = b"".join(_b(s) for s in seqs)
+        return self._ensemble(W, condition, context, with_probs,
+                              lambda c, cen, mea, st, P: lib().adx_ensemble_structures_batch(
+                                  self.ptr, W, seqbuf, c, context, gamma, cen, mea, st, P))
+
+    def walker_ensemble_structures(self, condition="apo", context=0, gamma=1.0, with_probs=False):
+        """The same for the walkers' current sequences."""
+        return self._ensemble(self.W, condition, context, with_probs,
+                              lambda c, cen, mea, st, P: lib().adx_walkers_ensemble_structures(
+                                  self.ptr, c, context, gamma, cen, mea, st, P))
+
+    def last_ensemble_ms(self):
+        """(outside-pass ms, structure-kernel ms) of the last ensemble_structures /
+        walker_ensemble_structures call, from HIP events."""
+        a, b = C.c_double(), C.c_double()
+        _check(lib().adx_last_ensemble_ms(self.ptr, C.byref(a), C.byref(b)))
         return a.value, b.value
 
     def walkers_init(self, seeds, seqs=None):

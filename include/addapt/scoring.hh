@@ -46,6 +46,15 @@ void set_parameter_file(const string &path);
 /// kT at 37 C in kcal/mol (scoring.cc:69-70).
 double kT();
 
+/// What RNAfold -p --MEA prints after the MFE line (GpuRnaFold::ensemble_structures).
+struct EnsembleStructures {
+    string centroid;        ///< the pairs with probability above 1/2
+    string mea;             ///< the maximum-expected-accuracy structure
+    double mea_value;       ///< its expected accuracy
+    double centroid_dist;   ///< the centroid's mean base-pair distance to the ensemble
+    double diversity;       ///< the ensemble's mean base-pair distance (vrna_mean_bp_distance)
+};
+
 class GpuRnaFold : public RnaFold {
 public:
     explicit GpuRnaFold(DeviceConstPtr device, AptamerConstPtr aptamer = nullptr, int gpu = 0);
@@ -59,6 +68,11 @@ public:
     /// optional hard constraint, and the ensemble energy in kcal/mol; the aptamer
     /// motif counts as in macrostate_prob.  Sample k under `seed` does not depend on n.
     std::pair<std::vector<string>, double> sample_structures(int n, uint64_t seed, string constraint = "") const;
+    /// The centroid and the MEA structure (weight gamma, RNAfold's default 1) of the
+    /// ensemble under an optional hard constraint, with the three statistics; the
+    /// aptamer motif counts as in macrostate_prob.  Both all '.' and the statistics
+    /// NaN when the constraint admits nothing.
+    EnsembleStructures ensemble_structures(double gamma = 1.0, string constraint = "") const;
 
 private:
     string seq_;

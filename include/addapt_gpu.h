@@ -98,6 +98,30 @@ adx_status adx_fold_mfe_structure(adx_fold *f, char *structure, float *energy_kc
  * admits no structure.  Filled (FP64) and sampled on the GPU. */
 adx_status adx_fold_sample_structures(adx_fold *f, int n_samples, uint64_t seed,
                                       char *structures, float *energy_kcal);
+/* What RNAfold -p --MEA prints after the MFE line, for the ensemble the compound
+ * describes (motif, constraint), from its pair probabilities P on the GPU:
+ *   centroid       the pairs with P > 1/2 (taken in ascending (i, j); a pair that
+ *                  shares a base with or crosses one already taken is dropped,
+ *                  which exact probabilities never need)
+ *   centroid_dist  sum_{i<j} (pair in centroid ? 1 - P : P)
+ *   diversity      2 sum_{i<j} P (1 - P)                 (vrna_mean_bp_distance)
+ *   MEA            the nested structure over pairs with P > 0 that maximises
+ *                  sum_{i unpaired} pu[i] + 2 gamma sum_{pairs} P[i][j],
+ *                  pu[i] = 1 - sum_j P[i][j]; mea is that maximum.  gamma = 1 is
+ *                  RNAfold's default.
+ * All FP64; ties go to a fixed candidate order, so equal inputs give equal bytes. */
+typedef struct adx_ensemble_stats {
+    double mea;
+    double centroid_dist;
+    double diversity;
+} adx_ensemble_stats;
+
+/* centroid and mea are strlen(seq)+1 bytes each, NUL-terminated; any of
+ * centroid, mea, stats may be NULL, not all.  A constraint that admits no
+ * structure: both all '.', the statistics NaN.  Fills the probabilities
+ * adx_fold_bpp serves as a by-product. */
+adx_status adx_fold_ensemble_structures(adx_fold *f, double gamma, char *centroid, char *mea,
+                                        adx_ensemble_stats *stats);
 /* fc->exp_matrices->probs[fc->iindx[i] - j] with 1-based i < j (:47-50);
  * computed on first use with md.compute_bpp (:41-44). */
 adx_status adx_fold_bpp(adx_fold *f, int i, int j, double *prob);
@@ -314,6 +338,29 @@ adx_status adx_walkers_sample_structures(adx_ctx *ctx, int variant, int n_sample
 /* Device time (ms, HIP events) of the context's last sampling call: the FP64
  * fill and the sampling kernel. */
 adx_status adx_last_sample_ms(const adx_ctx *ctx, double *fill_ms, double *sample_ms);
+
+/* Centroid and MEA structures (adx_fold_ensemble_structures) of W sequences
+ * (W*N chars) for the (context, condition) unconstrained fold, addressed as
+ * adx_bppm_batch addresses it: centroid, mea = W*L chars, no terminators;
+ * stats[W]; any of the three may be NULL, not all.  probs = W*L*L doubles,
+ * optional (NULL): the matrices the structures were computed from, as
+ * adx_bppm_batch lays them out.  The matrices stay on the device between the
+ * outside pass and the structure kernel.  ADX_FOLD_PF contexts only
+ * (ADX_EUNSUPPORTED on an MFE context).  Walker state, the stored tables and
+ * the next step's results are not touched. */
+adx_status adx_ensemble_structures_batch(adx_ctx *ctx, int n_walkers, const char *seqs, int condition,
+                                         int context, double gamma, char *centroid, char *mea,
+                                         adx_ensemble_stats *stats, double *probs);
+
+/* The same for the walkers' current sequences, read on the device
+ * (ADX_ESTATE before adx_walkers_init). */
+adx_status adx_walkers_ensemble_structures(adx_ctx *ctx, int condition, int context, double gamma,
+                                           char *centroid, char *mea, adx_ensemble_stats *stats,
+                                           double *probs);
+
+/* Device time (ms, HIP events) of the context's last ensemble-structures call:
+ * the outside pass and the structure kernel. */
+adx_status adx_last_ensemble_ms(const adx_ctx *ctx, double *bppm_ms, double *struct_ms);
 
 /* Variant v of the score: which (context, condition, macrostate or -1). */
 adx_status adx_variant_desc(const adx_ctx *ctx, int v, int *context, int *condition,
