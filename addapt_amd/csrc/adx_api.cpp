@@ -334,6 +334,7 @@ adx_status build_constraint(const std::string &cst, int N, std::vector<uint8_t> 
         if (c == 'x') flg[i] |= 1;
         if (c == '<') flg[i] |= 2;
         if (c == '>') flg[i] |= 4;
+        if (c == '|') flg[i] |= 8;
         if (c == '|' || c == '<' || c == '>' || partner[i]) unp[i] = 0;
     }
     std::vector<int> up(np + 1, 0), dn(np, 0);

@@ -132,7 +132,9 @@ __device__ __forceinline__ int special_hp(const uint32_t *spk, uint32_t key) {
 }
 
 // ---------------------------------------------------------------- hard constraints
-// flg bits: 1 = 'x' (no pair), 2 = '<' (pairs upstream), 4 = '>' (downstream);
+// flg bits: 1 = 'x' (no pair), 2 = '<' (pairs upstream), 4 = '>' (downstream),
+// 8 = '|' (pairs; allowed() does not read it, but the kernels' setup takes any
+// flag or partner as "this fold is constrained", and a '|' sets nothing else);
 // ptn = enforced partner (0 none); enc = innermost enclosing enforced pair id.
 // L: any LDS carve with the byte arrays flg, ptn, enc.
 template <class LT>

@@ -9,6 +9,11 @@ within the bound 1e-4 kcal/mol per fold induces (tests/parity_bounds.py:
 a pair probability is a ratio of two ensembles like a macrostate's); MC
 trajectories bit-exact with the oracle forced through Metropolis near-ties
 (|crit - u| <= 1e-6).
+
+Whole matrices under hard constraints (every constraint character, the motif
+with a constraint, lengths on both sides of bppm_kernel's layouts) also hold
+the derived bound on ln P from pair_probe.REL_FLOOR up and are exactly 0 where
+the oracle is; measured there: max |dP| and worst |d ln P| 6.2e-6.
 """
 import math
 import random
@@ -17,7 +22,9 @@ import numpy as np
 import pytest
 
 from addapt_amd import workloads
+from pair_probe import REL_FLOOR, can_pair
 from parity_bounds import close_score, close_term, score_bound
+from structure_check import cons, pin
 
 pytestmark = pytest.mark.gpu
 
@@ -215,3 +222,130 @@ def test_mc_pair_terms_full_size(native, oracle, N):
     for w in list(range(0, W, 683)) + [W - 1]:
         ref, tref = sf.score(final[w], [active])
         assert close_score(scores[w], ref, tref, terms), (N, w, scores[w], ref)
+
+
+# ------------------------------------------------------------------ whole matrices under hard constraints
+CST_LENGTHS = (20, 45, 64, 65, 100, 101, 128, 150, 152)
+CST_KINDS = ("cons", "pair", "xrun", "|", "<", ">", "pin")
+
+
+def _bpp_matrix(native, seq, cst=None, motif=None):
+    f = native.Fold(seq)
+    if motif:
+        f.add_motif(*motif)
+    if cst:
+        f.add_constraint(cst)
+    n = len(seq)
+    return np.array([[f.bpp(i + 1, j + 1) for j in range(n)] for i in range(n)])
+
+
+def _assert_matrix(got, ref, where):
+    """|dP| <= P_TOL everywhere, the derived bound on ln P from REL_FLOOR up,
+    exactly 0 where the oracle is exactly 0."""
+    err = np.abs(got - ref)
+    assert err.max() <= P_TOL, where + (float(err.max()),)
+    assert not got[ref == 0.0].any(), where + (np.argwhere((ref == 0.0) & (got != 0.0))[:4].tolist(),)
+    worst = 0.0
+    for i, j in np.argwhere(ref >= REL_FLOOR):
+        a = math.log(got[i, j]) if got[i, j] > 0.0 else -math.inf
+        b = math.log(ref[i, j])
+        assert close_term(a, b, True), where + ((int(i), int(j)), got[i, j], ref[i, j], abs(a - b))
+        worst = max(worst, abs(a - b))
+    print("CST", where, "max|dP| %.3e worst|dlnP| %.3e over %d" % (err.max(), worst, (ref >= REL_FLOOR).sum()))
+
+
+def _side_position(seq, P0, side):
+    """The position whose unconstrained pairing probability is nearest 0.5 among
+    those that can pair on `side` ("<": a partner before it, ">": after it, "|": either)."""
+    U = np.triu(P0, 1)                             # [i][j], i < j
+    up, down = U.sum(axis=0), U.sum(axis=1)
+    can = {"<": up > 0.0, ">": down > 0.0, "|": (up + down) > 0.0}[side]
+    tot = np.where(can, up + down, np.inf)
+    return int(np.argmin(np.abs(tot - 0.5)))
+
+
+def _constraint(oracle, rng, seq, kind):
+    n = len(seq)
+    if kind == "cons":
+        return cons(rng, seq)
+    if kind == "pair":      # one enforced pair of span >= n / 2 where the bases pair
+        i, j = rng.choice([(i, j) for i in range(n) for j in range(i + (n + 1) // 2, n) if can_pair(seq, i, j)])
+        return "." * i + "(" + "." * (j - i - 1) + ")" + "." * (n - j - 1)
+    if kind == "xrun":
+        a = rng.randrange(0, n - 9)
+        return "." * a + "x" * 10 + "." * (n - a - 10)
+    if kind == "pin":
+        return pin(oracle.mfe(seq)[1])
+    k = _side_position(seq, oracle.bppm(seq)[1], kind)
+    return "." * k + kind + "." * (n - k - 1)
+
+
+def _cst_sequence(oracle, N):
+    """A random sequence of length N whose MFE structure has a pair (to pin)."""
+    rng = random.Random(7000 + N)
+    while True:
+        seq = rand_seq(rng, N)
+        if "(" in oracle.mfe(seq)[1]:
+            return seq
+
+
+@pytest.mark.parametrize("kind", CST_KINDS)
+@pytest.mark.parametrize("N", CST_LENGTHS)
+def test_fold_bpp_constrained(native, oracle, N, kind):
+    """bppm_kernel under every hard-constraint character, at the lengths on both
+    sides of its layouts (64 / 65, 100 / 101, the global-scratch layout from 114)."""
+    seq = _cst_sequence(oracle, N)
+    rng = random.Random(N * 31 + CST_KINDS.index(kind))
+    cst = _constraint(oracle, rng, seq, kind)
+    assert len(cst) == N
+    _, ref = oracle.bppm(seq, cst)
+    assert ref.any(), (N, kind, cst)                # the constraint admits structures
+    got = _bpp_matrix(native, seq, cst)
+    _assert_matrix(got, ref, (N, kind, cst))
+    if kind in "|<>":
+        k = cst.index(kind)
+        up, down = got[:k, k].sum(), got[k, k + 1:].sum()
+        assert abs(up + down - 1.0) <= N * P_TOL, (N, kind, k, up, down)
+        if kind == "<":
+            assert down == 0.0 and ref[k, k + 1:].sum() == 0.0, (N, k, down)
+        if kind == ">":
+            assert up == 0.0 and ref[:k, k].sum() == 0.0, (N, k, up)
+    if kind == "pin":
+        s = oracle.mfe(seq)[1]
+        assert "(" in s
+        st, paired = [], np.zeros((N, N), bool)
+        for k, c in enumerate(s):
+            if c == "(":
+                st.append(k)
+            elif c == ")":
+                paired[st.pop(), k] = True
+        up = np.triu(np.ones((N, N), bool), 1)
+        assert (got[paired] >= 1.0 - P_TOL).all() and (got[up & ~paired] <= P_TOL).all(), (N, s)
+
+
+@pytest.mark.parametrize("tail", [17, 111])
+def test_fold_bpp_constrained_motif(native, oracle, tail):
+    """A constraint on the flanks together with the ligand motif (56 and 150 nt)."""
+    rng = random.Random(9000 + tail)
+    apt, fold = workloads.THEO_SEQ, workloads.THEO_FOLD
+    left, right = rand_seq(rng, 12), rand_seq(rng, tail)
+    seq = left + apt + right
+    cst = cons(rng, left) + "." * len(apt) + cons(rng, right)
+    assert set(cst) > {"."}
+    e = oracle.theo_bonus()
+    _, ref = oracle.bppm(seq, cst, oracle.make_motif(apt, fold, e))
+    _, bare = oracle.bppm(seq, cst)
+    assert ref.max() > 0.5 and np.abs(ref - bare).max() > 0.01     # the motif matters here
+    got = _bpp_matrix(native, seq, cst, (apt, fold, e))
+    _assert_matrix(got, ref, (len(seq), "motif", cst))
+
+
+def test_fold_bpp_infeasible_101(native, oracle):
+    """An enforced pair of bases that cannot pair: nothing is admissible, every probability is 0."""
+    rng = random.Random(101)
+    seq = "A" + rand_seq(rng, 99) + "A"
+    cst = "(" + "." * 99 + ")"
+    _, ref = oracle.bppm(seq, cst)
+    assert not ref.any()
+    got = _bpp_matrix(native, seq, cst)
+    assert not got.any(), np.argwhere(got != 0.0)[:4].tolist()
