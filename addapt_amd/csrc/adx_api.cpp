@@ -427,6 +427,7 @@ struct Problem {
     DevBuf<int> dChg;
     DevBuf<int> dOrder;          // launch order of a rescore's folds (KArgs::order, order_kernel)
     DevBuf<uint8_t> dCls;        // the folds' weight classes (KArgs::ocls, the proposals' or a rescore's)
+    DevBuf<int> dPairQ;          // mfe_pair_kernel's work queue (KArgs::pairq)
     DevBuf<int> dTrace;          // c / fm / fm1 scratch of mfe_trace_kernel, one launch chunk
     DevBuf<double> dSample;      // qb / qm / qm1 / q5 scratch of pf_fill_kernel, one launch chunk
     float sample_fill_ms = 0.f, sample_draw_ms = 0.f;   // the last sample() call, from HIP events
@@ -494,6 +495,7 @@ struct Problem {
         ka.chg = st ? dChg.p : nullptr;
         ka.order = st && !std::getenv("ADX_NO_ORDER") ? dOrder.p : nullptr;
         ka.ocls = dCls.p;
+        ka.pairq = dPairQ.p;
         ka.gstep = dGstep.p;
         ka.pf_ring = pf_ring ? 1 : 0;
         ka.ring_scratch = dRingScr.p;
@@ -814,6 +816,10 @@ struct Problem {
     adx_status prepare(int W) {
         adx_status so = ensure_ovf(W);
         if (so) return so;
+        if (mfe16 && !dPairQ.p) {
+            HIP_TRY(dPairQ.alloc(2));
+            HIP_TRY(hipMemsetAsync(dPairQ.p, 0, sizeof(int) * 2, stream));
+        }
         so = ensure_gstep(W);
         if (so) return so;
         if (pf_ring) {   // qb scratch of the stateless ring folds

@@ -204,6 +204,10 @@ struct KArgs {
     // (fold_common.hpp walker_at); null: blockIdx order
     int *order;
     const uint8_t *ocls;
+    // mfe_pair_kernel's work queue (two ints): [0] the next item a workgroup
+    // takes (atomicAdd), zero before every launch; [1] the scored walkers of the
+    // order list, the items' bound when there is one (order_kernel sets both)
+    int *pairq;
     // MC steps: the scores a fold launch leaves as per-variant energies in gstep
     // are combined by the step's tail (mc_step.hip accept_walker), not by a
     // combine_kernel launch of their own

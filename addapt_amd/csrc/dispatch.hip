@@ -62,6 +62,14 @@ static bool mfe_pair_active(const KArgs &k16) {
     const char *e = std::getenv("ADX_MFE_PAIR");
     return !(e && e[0] == '0') && mfe_pair_covers(k16);
 }
+// ADX_PAIR_GRID=n: mfe_pair_kernel's workgroup count (default 0: as many as are
+// resident at once).  The folds do not depend on it; a test sets 1 so that one
+// workgroup takes every item of the queue in turn
+static int mfe_pair_grid() {
+    const char *e = std::getenv("ADX_PAIR_GRID");
+    const int n = e ? std::atoi(e) : 0;
+    return n > 0 ? n : 0;
+}
 
 static KArgs packed16(const KArgs &ka) {   // the packed 16-bit MFE kernels' energy tables
     KArgs k16 = ka;
@@ -138,7 +146,7 @@ hipError_t launch_score_m(const KArgs &ka, const uint8_t *seqs, int W, double *s
                 e = hipMemsetAsync(ka.ovf, 0, sizeof(int) * size_t(W), stream);
                 if (e != hipSuccess) return e;
             }
-            e = mfe_pair_active(k16) ? launch_mfe_pair(k16, seqs, W, g, mask, stream)
+            e = mfe_pair_active(k16) ? launch_mfe_pair(k16, seqs, W, g, mask, stream, mfe_pair_grid())
                                      : launch_mfe_cells(k16, seqs, W, g, mask, stream);
             if (e == hipSuccess) e = combine();
         } else {

@@ -57,8 +57,9 @@ size_t mfe_cells_lds(const KArgs &ka);
 hipError_t launch_mfe_cells(const KArgs &ka, const uint8_t *seqs, int W, float *gout, const int *mask,
                             hipStream_t stream);
 bool mfe_pair_covers(const KArgs &ka);
+// grid > 0: that many workgroups instead of one per resident slot (ADX_PAIR_GRID, dispatch.hip)
 hipError_t launch_mfe_pair(const KArgs &ka, const uint8_t *seqs, int W, float *gout, const int *mask,
-                           hipStream_t stream);
+                           hipStream_t stream, int grid = 0);
 
 // ---- mfe_trace.hip: MFE structures (fill + traceback, one workgroup per sequence)
 size_t mfe_trace_slice_ints(const KArgs &ka);   // ints of HBM scratch per workgroup

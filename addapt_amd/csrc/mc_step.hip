@@ -507,7 +507,10 @@ __global__ void __launch_bounds__(TAIL_WPB * 64) step_tail_kernel(StepArgs st, K
 // launch.  One workgroup, LDS counters, the class bases by one wave's scan;
 // the order within a class does not matter (each walker's fold is independent
 // of where it runs).
-__global__ void __launch_bounds__(1024) order_kernel(int W, const uint8_t *cls, int *order) {
+// pairq (KArgs::pairq, may be null): the scored walkers' count bounds mfe_pair_kernel's
+// work queue, whose counter starts at zero -- this kernel runs before the folds
+// in the same stream.
+__global__ void __launch_bounds__(1024) order_kernel(int W, const uint8_t *cls, int *order, int *pairq) {
     __shared__ int hist[65];
     const int tid = threadIdx.x;
     if (tid < 65) hist[tid] = 0;
@@ -524,7 +527,13 @@ __global__ void __launch_bounds__(1024) order_kernel(int W, const uint8_t *cls, 
             if (tid >= o) incl += t;
         }
         hist[tid] = incl - h;
-        if (tid == WAVE - 1) hist[64] = incl;
+        if (tid == WAVE - 1) {
+            hist[64] = incl;
+            if (pairq) {
+                pairq[0] = 0;
+                pairq[1] = incl;
+            }
+        }
     }
     __syncthreads();
 #pragma unroll 4
@@ -539,7 +548,8 @@ __global__ void __launch_bounds__(1024) order_kernel(int W, const uint8_t *cls, 
 static hipError_t launch_window(const KArgs &ka, const StepArgs &st, const int *changed, double *tv,
                                 hipStream_t stream, hipEvent_t *evs) {
     if (evs) (void)hipEventRecord(evs[0], stream);
-    if (ka.order) hipLaunchKernelGGL(order_kernel, dim3(1), dim3(1024), 0, stream, st.W, ka.ocls, ka.order);
+    if (ka.order) hipLaunchKernelGGL(order_kernel, dim3(1), dim3(1024), 0, stream, st.W, ka.ocls, ka.order,
+                                     ka.pairq);
     hipError_t e;
     if (ka.n_pairs > 0 && ka.mode == 0 && ka.tab && ka.gstep) {
         // inside folds first (they write the proposal's tables), then the outside

@@ -293,6 +293,79 @@ __device__ __forceinline__ void q5_start(const LT &L, int N) {
     for (int j = 1; j <= 4 && j <= N; j++) L.q5[j] = (L.up[j] >= 1) ? L.q5[j - 1] : INF16;
 }
 
+// fold_writeback_once's pass over the fold's whole vectors of V (n words each) of the
+// three tables: every element read from LDS once, checked and, with a slot to
+// write (dp; Cs words between its tables), stored.  Returns the cells done
+template <class V, int NT, class LT>
+__device__ __forceinline__ int writeback_vectors(const LT &L, u32 *dp, size_t Cs, int C, int tid, bool &low) {
+    constexpr int n = int(sizeof(V) / sizeof(u32));
+    const int nv = C / n;   // n = 1, 2, 4: a shift
+    for (int k = tid; k < nv; k += NT) {
+        const V a = reinterpret_cast<const V *>(L.qbm)[k];
+        const V b = reinterpret_cast<const V *>(L.qm)[k];
+        const V c = reinterpret_cast<const V *>(L.qm1)[k];
+        u32 e[3 * n];
+        __builtin_memcpy(e, &a, sizeof a);
+        __builtin_memcpy(e + n, &b, sizeof b);
+        __builtin_memcpy(e + 2 * n, &c, sizeof c);
+#pragma unroll
+        for (int t = 0; t < 3 * n; t++) low |= mfe16_inexact(sv(e[t]));
+        if (dp) {
+            reinterpret_cast<V *>(dp)[k] = a;
+            reinterpret_cast<V *>(dp + Cs)[k] = b;
+            reinterpret_cast<V *>(dp + 2 * Cs)[k] = c;
+        }
+    }
+    return nv * n;
+}
+
+// mfe_pair.hip's write-back (tid: the thread's index).  The fold's cells of the
+// three tables, q5 and the codes to the slot the fold writes (the next proposal's
+// unchanged cells; a restore reads no cell past the fold's own), and the
+// exactness guard, as fold_writeback below, in one pass: each element
+// is read from LDS once, checked and stored, in the widest vectors that the LDS
+// tables, the slot and its table stride (ka.cells) are all aligned for -- 16
+// bytes at Nmax = 100 for a walker's even fold groups, 8 for the odd ones, whose
+// slot starts 3 cells + Nmax + 2 words later; the cells past the last whole
+// vector, and every cell of a layout aligned to 4 bytes only, go one by one.
+// (Two passes with 4-byte accesses before; a merged pass that found each
+// element's table by a division measured -1.2 % in round 6.)  mfe_cells.hip keeps
+// the two passes: at Nmax = 150 the slot's tables are aligned to 4 bytes only
+// (10731 cells), and this function's one-by-one loop measured -3.2 % on the
+// 150-nt bench line.  Returns this thread's part of the guard; the caller ORs it
+// over the workgroup
+template <int NT, class LT>
+__device__ __forceinline__ bool fold_writeback_once(const KArgs &ka, const LT &L, const IncM &inc, int N, int tid) {
+    const int C = ((N - 4) * (N - 3)) >> 1;
+    const size_t Cs = size_t(ka.cells);
+    u32 *dp = inc.dst;
+    bool low = false;
+    const uint32_t al = uni(int(uint32_t(uintptr_t(dp)) | uint32_t(Cs * 4) | lds_addr(L.qbm) | lds_addr(L.qm) |
+                                lds_addr(L.qm1)));
+    int done = 0;
+    if ((al & 15u) == 0) done = writeback_vectors<uint4, NT>(L, dp, Cs, C, tid, low);
+    else if ((al & 7u) == 0) done = writeback_vectors<uint2, NT>(L, dp, Cs, C, tid, low);
+    for (int k = done + tid; k < C; k += NT) {
+        const u32 a = L.qbm[k], b = L.qm[k], c = L.qm1[k];
+        low |= mfe16_inexact(sv(a)) || mfe16_inexact(sv(b)) || mfe16_inexact(sv(c));
+        if (dp) {
+            dp[k] = a;
+            dp[Cs + k] = b;
+            dp[2 * Cs + k] = c;
+        }
+    }
+    for (int k = tid; k <= N; k += NT) {
+        const u32 q = L.q5[k];
+        low |= mfe16_inexact(sv(q));
+        if (dp) dp[3 * Cs + k] = q;
+    }
+    if (dp) {
+        const int C16 = (C + 15) >> 4;
+        for (int k = tid; k < C16; k += NT) inc.cc_dst[k] = reinterpret_cast<const uint4 *>(L.cc)[k];
+    }
+    return low;
+}
+
 // After the sweep: the three tables, q5 and the codes to the slot the fold
 // writes (the next proposal's unchanged cells), and the exactness guard of the
 // 16-bit encoding, every stored value >= floor.  Returns this thread's part of

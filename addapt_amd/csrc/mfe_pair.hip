@@ -38,6 +38,7 @@
 // and its launcher.  mfe_common.hpp holds what mfe_cells.hip spells alike.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -117,7 +118,7 @@ struct CP {
     u32 *pos;              // [np]: S | flg << 3 | up << 8 | ptn << 16 | enc << 24 (the per-cell pass)
     uint8_t *cl;           // [3][2 np]: rows of the pairable cells of a step's two diagonals, by step % 3
     int *cnt;              // [3]: cells of the step's first diagonal | of both << 16
-    int *flag;             // [2]: block_or words (constrained, 16-bit range left)
+    int *flag;             // [3]: block_or words (constrained, 16-bit range left), the item's queue index
     u32 *rec;              // [3][2][64]: the B cells' setup (rank < 64 over both diagonals) by step % 3:
                            //   i | oc << 8 | A << 16 | B << 24 and mismatchI(oc) | mismatch1n(oc) +
                            //   mismatchI(oc) << 16 (MFE table entries are equal in both halves)
@@ -255,6 +256,47 @@ __device__ __forceinline__ void cell_pass(const CP &L, const Band &bd, int lane,
     }
 }
 
+// What is the same for every fold of a launch, stored once per workgroup before
+// its first item (no fold writes these regions): the energy tables ct, dt and e4
+// (the generic interior energies of the 4-lane blocks) and the impossible span-3
+// diagonal in front of qbm with its codes in front of cc.  Every load is in flight
+// before the first store; the caller's next barrier orders the stores.
+template <int NT, int NM>
+__device__ __forceinline__ void pair_constants(const DevScaled *__restrict__ XS, const DevTables *__restrict__ TT,
+                                               const CP &L) {
+    static_assert(NT >= 288 && NT >= MFE_E4_SLOTS * 4, "one table element per thread");
+    const int tid = threadIdx.x;
+    const u32 *gct = reinterpret_cast<const u32 *>(XS->ctab);
+    constexpr int NCT = (CT_SIZE + NT - 1) / NT;
+    u32 v_ct[NCT];
+#pragma unroll
+    for (int t = 0; t < NCT; t++) v_ct[t] = gct[min(tid + t * NT, CT_SIZE - 1)];
+    const DevTables &T0 = *TT;
+    const u32 v_mh = __float_as_uint((&T0.mmH[0][0][0])[min(tid, 199)]);
+    const u32 v_mi = __float_as_uint((&T0.mmI[0][0][0])[min(tid, 199)]);
+    const u32 v_ms = __float_as_uint((&T0.mlstem[0][0][0])[min(tid, 199)]);
+    const u32 v_ex = __float_as_uint((&T0.ext[0][0][0])[min(tid, 287)]);
+    const u32 v_tau = __float_as_uint(T0.termAU[tid & 7]);
+    const int ke = min(tid, MFE_E4_SLOTS * 4 - 1);
+    const int e4a = MFE_E4_A[ke >> 2][ke & 3], e4u = MFE_E4_U[ke >> 2];
+    const u32 v_e4 = XS->ku16[e4u][max(e4a, 0)];
+#pragma unroll
+    for (int t = 0; t < NCT; t++)
+        if (tid + t * NT < CT_SIZE) L.ct[tid + t * NT] = v_ct[t];
+    if (tid < 200) {
+        L.dt[DT_MMH + tid] = v_mh;
+        L.dt[DT_MMI + tid] = v_mi;
+        L.dt[DT_MLS + tid] = v_ms;
+    }
+    if (tid < 288) L.dt[DT_EXT + tid] = v_ex;
+    if (tid < 8) L.dt[DT_TAU + tid] = v_tau;
+    if (tid < MFE_E4_SLOTS * 4) L.e4[tid] = e4a < 0 ? INF16 : v_e4;
+    for (int k = tid; k < NM - 3; k += NT) {   // (B's d-lanes reach the span-3 diagonal)
+        (L.qbm - (NM - 3))[k] = INF16;
+        (L.cc - (NM - 3))[k] = 0;
+    }
+}
+
 // The fold's setup (sequence, tables, refold restore, per-cell pass) and its
 // write-back run in the kernel body, one copy of the code for all eight waves
 // (round 6: as part of the per-wave instances each wave fetched its own copy,
@@ -263,16 +305,17 @@ __device__ __forceinline__ void cell_pass(const CP &L, const Band &bd, int lane,
 template <int NT, int NM>
 __device__ __forceinline__ bool pair_setup(const KArgs &ka, const DevScaled *__restrict__ XS,
                                            const DevTables *__restrict__ TT, const int *vs, const uint8_t *raw,
-                                           const CP &L, const IncM &inc, unsigned long long *sst) {
+                                           const CP &L, const IncM &inc, const int tid,
+                                           unsigned long long *sst) {
     static_assert(NT == NWV * WAVE, "one wave per block slot");
-    const DevVariant V = ka.variants[vs[0]];
-    const bool mh0 = ka.variants[vs[0]].motif != 0, mh1 = ka.variants[vs[1]].motif != 0;
+    // (uni(): the kernel's loop makes every load from global memory a vector load)
+    DevVariant V = ka.variants[vs[0]];
+    V.ctx = uni(V.ctx), V.cons_off = uni(V.cons_off);
+    const bool mh0 = uni(V.motif) != 0, mh1 = uni(ka.variants[vs[1]].motif) != 0;
     const int N = uni(V.N);
-    const int tid = threadIdx.x;
     const int lane = tid & (WAVE - 1);
     const int wid = uni(tid / WAVE);
     const int NP = L.np;
-    const u32 *gct = reinterpret_cast<const u32 *>(XS->ctab);
 #ifdef ADX_STAMP
     const unsigned long long st_setup0 = __builtin_amdgcn_s_memtime();
 #endif
@@ -284,22 +327,9 @@ __device__ __forceinline__ bool pair_setup(const KArgs &ka, const DevScaled *__r
     // thread stores, all in flight at once and stored before the restore's loads are
     // issued (the kernel prologue's loop per table waited on each load in turn, and the
     // setup tables' loads waited behind the restore's)
-    static_assert(NT >= 288 && NT >= MAX_SPECIAL_HP && NT >= MAX_MOTIF && NT >= MFE_E4_SLOTS * 4 && NT >= NM + 2,
-                  "one setup element per thread");
-    constexpr int NCT = (CT_SIZE + NT - 1) / NT;
-    u32 v_ct[NCT];
-#pragma unroll
-    for (int t = 0; t < NCT; t++) v_ct[t] = gct[min(tid + t * NT, CT_SIZE - 1)];
-    const DevTables &T0 = *TT;
-    const u32 v_mh = __float_as_uint((&T0.mmH[0][0][0])[min(tid, 199)]);
-    const u32 v_mi = __float_as_uint((&T0.mmI[0][0][0])[min(tid, 199)]);
-    const u32 v_ms = __float_as_uint((&T0.mlstem[0][0][0])[min(tid, 199)]);
-    const u32 v_ex = __float_as_uint((&T0.ext[0][0][0])[min(tid, 287)]);
-    const u32 v_tau = __float_as_uint(T0.termAU[tid & 7]);
+    static_assert(NT >= MAX_SPECIAL_HP && NT >= MAX_MOTIF && NT >= NM + 2, "one setup element per thread");
     const u32 v_hp = __float_as_uint(XS->hp[min(tid, N)]);   // hairpin length factors (per-cell pass)
-    const int ke = min(tid, MFE_E4_SLOTS * 4 - 1);
-    const int e4a = MFE_E4_A[ke >> 2][ke & 3], e4u = MFE_E4_U[ke >> 2];
-    const int n_sp = XS->n_special;
+    const int n_sp = uni(XS->n_special);
     const uint32_t v_spk = XS->sp_key[min(tid, MAX_SPECIAL_HP - 1)];
     const u32 v_spv = __float_as_uint(XS->sp_val[min(tid, MAX_SPECIAL_HP - 1)]);
     const uint8_t v_mc = XS->motif_code[min(tid, MAX_MOTIF - 1)];
@@ -338,16 +368,6 @@ __device__ __forceinline__ bool pair_setup(const KArgs &ka, const DevScaled *__r
         L.pos[tid] = u32(v_sw) | (u32(v_fl & 7) << 3) | (u32(v_up) << 8) | (u32(v_pt) << 16) | (u32(v_en) << 24);
     }
     const bool cst = tid >= 1 && tid <= N && (v_fl || v_pt);
-#pragma unroll
-    for (int t = 0; t < NCT; t++)
-        if (tid + t * NT < CT_SIZE) L.ct[tid + t * NT] = v_ct[t];
-    if (tid < 200) {
-        L.dt[DT_MMH + tid] = v_mh;
-        L.dt[DT_MMI + tid] = v_mi;
-        L.dt[DT_MLS + tid] = v_ms;
-    }
-    if (tid < 288) L.dt[DT_EXT + tid] = v_ex;
-    if (tid < 8) L.dt[DT_TAU + tid] = v_tau;
     u32 *hpf = L.colmin;   // the U slots' space until the sweep (initialised after the per-cell pass)
     static_assert(4 * (NM + 2) >= NM + 1, "hairpin factors fit the U slots");
     if (tid <= N) hpf[tid] = v_hp;
@@ -366,16 +386,11 @@ __device__ __forceinline__ bool pair_setup(const KArgs &ka, const DevScaled *__r
         mcode[tid] = v_mc;
         mpt[tid] = v_mp;
     }
-    for (int k = tid; k < NM - 3; k += NT) {   // the impossible span-3 diagonal (B's d-lanes reach it)
-        (L.qbm - (NM - 3))[k] = INF16;
-        (L.cc - (NM - 3))[k] = 0;
-    }
 
     // ---- refold restore: the loads of all three tables (8-byte vector loads into
     // registers), stored to LDS after the motif scan, so their HBM latency overlaps
     // it (round 6; the loop of dependent load -> store pairs cost ~20k cycles per
-    // fold group).  The generic interior energies of the 4-lane blocks (e4) ride along.
-    const u32 v_e4 = XS->ku16[e4u][max(e4a, 0)];
+    // fold group).
     constexpr int CNM = ((NM - 4) * (NM - 3)) >> 1;
     constexpr int RS = (3 * (CNM >> 1) + NT - 1) / NT;   // loads per thread
     const int Crs = ((N - 4) * (N - 3)) >> 1, half = Crs >> 1;
@@ -411,7 +426,7 @@ __device__ __forceinline__ bool pair_setup(const KArgs &ka, const DevScaled *__r
     const unsigned long long st_s1 = __builtin_amdgcn_s_memtime();   // setup tables stored, restore issued
 #endif
     const bool constrained = block_or(L.flag, cst);
-    const int mL = XS->motif_len;
+    const int mL = uni(XS->motif_len);
 #ifdef ADX_STAMP
     const unsigned long long st_s2 = __builtin_amdgcn_s_memtime();   // sequence, constraints
 #endif
@@ -461,7 +476,6 @@ __device__ __forceinline__ bool pair_setup(const KArgs &ka, const DevScaled *__r
         }
         if (tid <= m_lo - 2 && tid <= N) L.q5[tid] = r5;
     }
-    if (tid < MFE_E4_SLOTS * 4) L.e4[tid] = e4a < 0 ? INF16 : v_e4;
     // the per-cell pass's quarter-sets (below): diagonal d's band rows in sets of 16,
     // listed diagonal by diagonal in the split slots' space (free until the sweep)
     // by the waves of lane-sets 0, 1 of the diagonals: qtab[k] = d | first row << 8
@@ -486,7 +500,7 @@ __device__ __forceinline__ bool pair_setup(const KArgs &ka, const DevScaled *__r
     }
     tot = uni(tot);
     __syncthreads();
-    const u32 mx = __float_as_uint(XS->motif_extra);
+    const u32 mx = u32(uni(int(__float_as_uint(XS->motif_extra))));
     const u32 mextra = (mh0 ? (mx & 0xFFFFu) : 0x7FFFu) | (mh1 ? (mx & 0xFFFF0000u) : 0x7FFF0000u);
     if (tid == 0) q5_start(L, N);
 #ifdef ADX_STAMP
@@ -1097,19 +1111,21 @@ __device__ __forceinline__ void q5_columns(const CP &L, const Band &bd, int d, i
 template <int NT, int NM, int WID>
 __device__ __forceinline__ void mfe_pair_fold(const KArgs &ka, const DevScaled *__restrict__ XS,
                                               const DevTables *__restrict__ TT, const int *vs, const CP &L,
-                                              const IncM &inc, const bool constrained, const unsigned long long *sst) {
+                                              const IncM &inc, const bool constrained, const int lane,
+                                              const unsigned long long *sst) {
     const DevVariant V = ka.variants[vs[0]];
     const int N = uni(V.N);
-    const int lane = threadIdx.x & (WAVE - 1);
     constexpr int wid = WID;
     constexpr int fls = FW[0] == wid ? 0 : (FW[1] == wid ? 1 : -1);   // this wave's finalize lane-set
     const u32 *gct = reinterpret_cast<const u32 *>(XS->ctab);
     const Band bd = inc.band(N);
-    const u32 mlclosing = __float_as_uint(XS->mlclosing);
-    const u32 mlbase = __float_as_uint(XS->mlbase_sig);
-    const u32 tauE = gct[CT_FSM + 6];
-    const u32 fsm5 = gct[CT_FSM + 5];
+    // (uni(): vector loads inside the kernel's loop, scalar registers through the sweep)
+    const u32 mlclosing = u32(uni(int(__float_as_uint(XS->mlclosing))));
+    const u32 mlbase = u32(uni(int(__float_as_uint(XS->mlbase_sig))));
+    const u32 tauE = u32(uni(int(gct[CT_FSM + 6])));
+    const u32 fsm5 = u32(uni(int(gct[CT_FSM + 5])));
     BUni U = buni(L, XS, N);
+    U.fs1 = u32(uni(int(U.fs1)));
     if (wid == L_WAVE) {   // steps 0 (no B work: d + 1 < 8) and 1
         if (lane == 0) L.cnt[0] = 0;
         build_list(L, bd, lane, 8, 1);
@@ -1179,52 +1195,130 @@ template <int NT, int NM, int... Ws>
 __device__ __forceinline__ void pair_fold_wave(std::integer_sequence<int, Ws...>, int w, const KArgs &ka,
                                                const DevScaled *__restrict__ XS, const DevTables *__restrict__ TT,
                                                const int *vs, const CP &L, const IncM &inc, bool constrained,
-                                               const unsigned long long *sst) {
-    ((w == Ws ? (mfe_pair_fold<NT, NM, Ws>(ka, XS, TT, vs, L, inc, constrained, sst), 0) : 0), ...);
+                                               int lane, const unsigned long long *sst) {
+    ((w == Ws ? (mfe_pair_fold<NT, NM, Ws>(ka, XS, TT, vs, L, inc, constrained, lane, sst), 0) : 0), ...);
 }
+
+// mfe_pair_kernel's arguments, one struct at the start of the argument segment
+struct PairArgs {
+    KArgs ka;
+    const DevScaled *XS;
+    const DevTables *TT;
+    const uint8_t *seqs;   // [W][ka.Nraw]
+    int W;
+    float *gout;           // [W][ka.n_variants]
+    const int *mask;       // 1 = fold (null: every walker)
+};
+static_assert(sizeof(PairArgs) % 4 == 0, "whole words");
+struct ArgWords {
+    uint32_t w[sizeof(PairArgs) / 4];
+};
 
 template <int NT, int NM>
 __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MFE_WPE, MFE_WPE)))
-mfe_pair_kernel(const KArgs ka, const DevScaled *__restrict__ XS, const DevTables *__restrict__ TT, const uint8_t *seqs,
-                int W, float *gout, const int *mask) {
-    // one workgroup per (walker, fold group), as mfe_cells_kernel
+mfe_pair_kernel(const PairArgs args) {
+    // Persistent workgroups over a queue of (walker, fold group) items in launch
+    // order: item it is group it % ng of the walker at launch position it / ng
+    // (ka.order: heaviest refolds first, the unscored walkers last and past the
+    // bound).  Thread 0 takes the next index from the counter ka.pairq[0] and hands
+    // it to the workgroup through the third word at PLay::FLAG.  No workgroup waits
+    // for another, and every pass of the loop consumes one index of a counter that
+    // only grows, so the loop ends after at most `items` passes whatever the number
+    // of workgroups or their residency.  Every exit from the body is uniform (the
+    // body has barriers): it and the walker's words are the same in every lane.
+    //
+    // The arguments are read again in every pass, through a pointer to the kernel's
+    // argument segment that the compiler cannot see through: hoisted out of the loop,
+    // the words a fold uses stay live across its whole sweep (measured at compile
+    // time: 130 spilled SGPRs and 39 spilled VGPRs instead of 15 and none).
+    // The thread's index goes the same way, or everything a fold derives from it
+    // alone is computed once before the loop and kept in registers throughout.
     const CP L = PLay<NM>::carve();
-    const int ng = ka.n_groups2;
-    const int wb = int(blockIdx.x) / ng, g = int(blockIdx.x) % ng;
-    if (wb >= W) return;
-    const WalkerRef wr = walker_ref(ka, mask, wb);   // heaviest refolds first
-    if (!wr.on) return;
-    const int w = wr.w;
-    if (threadIdx.x < 2) L.flag[threadIdx.x] = 0;
-    __syncthreads();
-    const int vs[2] = {ka.groups2[2 * g], ka.groups2[2 * g + 1]};
-    IncM inc{nullptr, nullptr, 0, 0, nullptr, nullptr};
-    if (ka.tab) {
-        inc = inc_slots(ka, w, g, wr.cur);
-        // a sibling group may clear tab_valid[w] on overflow while this one reads it:
-        // either value is correct (an incremental refold equals a fold from scratch)
-        if (wr.valid && wr.c0 >= 0)
-            inc_refold(inc, ka, w, g, wr.cur, wr.c0, wr.c1, ka.variants[vs[0]].before_len);
+    const int tid0 = threadIdx.x;
+    const int ng = args.ka.n_groups2, W = args.W;
+    const int items = (args.ka.order ? uni(min(max(args.ka.pairq[1], 0), W)) : W) * ng;
+    int *const queue = args.ka.pairq;
+    int nxt = 0;   // thread 0: the index of the item after this one, taken a whole fold ahead
+    if (tid0 == 0) nxt = atomicAdd(queue, 1);
+    pair_constants<NT, NM>(args.XS, args.TT, L);
+    typedef __attribute__((address_space(4))) const PairArgs *kernarg_ptr;
+    kernarg_ptr ap = (kernarg_ptr)__builtin_amdgcn_kernarg_segment_ptr();   // `args` sits at its start
+    for (;;) {
+        int tid = tid0;
+        asm volatile("" : "+s"(ap), "+v"(tid));
+        ArgWords aw;   // (scalar loads; the words no pass uses are dropped)
+#pragma unroll
+        for (int k = 0; k < int(sizeof(PairArgs) / 4); k++) aw.w[k] = reinterpret_cast<const kc_u32 *>(ap)[k];
+        const PairArgs A = __builtin_bit_cast(PairArgs, aw);
+        const KArgs &ka = A.ka;
+        const DevScaled *__restrict__ XS = A.XS;
+        const DevTables *__restrict__ TT = A.TT;
+        const uint8_t *seqs = A.seqs;
+        float *gout = A.gout;
+        const int *mask = A.mask;
+        __syncthreads();   // the item before is done with the tables and the block_or words
+        if (tid < 2) L.flag[tid] = 0;
+        if (tid == 0) L.flag[2] = nxt;
+        __syncthreads();
+        const int it = uni(L.flag[2]);
+        if (it >= items) break;
+        if (tid == 0) nxt = atomicAdd(queue, 1);
+        const int wb = it / ng, g = it - wb * ng;
+        // (after the first pass's stores a load from global memory is a vector load
+        // whatever its address: uni() puts what is uniform back into scalar registers)
+        const WalkerRef wr = walker_ref(ka, mask, wb);
+        if (!uni(int(wr.on))) continue;   // without an order list: a walker the mask leaves out
+        const int w = uni(wr.w), cur = uni(wr.cur), c0 = uni(wr.c0), c1 = uni(wr.c1);
+        const bool valid = uni(int(wr.valid)) != 0;
+        const int vs[2] = {uni(ka.groups2[2 * g]), uni(ka.groups2[2 * g + 1])};
+        IncM inc{nullptr, nullptr, 0, 0, nullptr, nullptr};
+        if (ka.tab) {
+            inc = inc_slots(ka, w, g, cur);
+            // a sibling group may clear tab_valid[w] on overflow while this one reads it:
+            // either value is correct (an incremental refold equals a fold from scratch)
+            if (valid && c0 >= 0) inc_refold(inc, ka, w, g, cur, c0, c1, uni(ka.variants[vs[0]].before_len));
+        }
+        unsigned long long sst[7] = {0, 0, 0, 0, 0, 0, 0};
+        const bool constrained = pair_setup<NT, NM>(ka, XS, TT, vs, seqs + size_t(w) * ka.Nraw, L, inc, tid, sst);
+        pair_fold_wave<NT, NM>(std::make_integer_sequence<int, NWV>{}, uni(tid / WAVE), ka, XS, TT, vs, L, inc,
+                               constrained, tid & (WAVE - 1), sst);
+        // the fold's write-back and 16-bit range check (one copy for all waves)
+        const int N = uni(ka.variants[vs[0]].N);
+        const u32 z = L.q5[N];
+        const bool bad = block_or(L.flag + 1, fold_writeback_once<NT>(ka, L, inc, N, tid));   // (mfe_cells.hip: __syncthreads_or)
+        if (tid == 0) fold_result(ka, w, vs, gout, z, bad);
     }
-    unsigned long long sst[7] = {0, 0, 0, 0, 0, 0, 0};
-    const bool constrained = pair_setup<NT, NM>(ka, XS, TT, vs, seqs + size_t(w) * ka.Nraw, L, inc, sst);
-    pair_fold_wave<NT, NM>(std::make_integer_sequence<int, NWV>{}, uni(int(threadIdx.x) / WAVE), ka, XS, TT, vs, L,
-                           inc, constrained, sst);
-    // the fold's write-back and 16-bit range check (one copy for all waves)
-    const int N = uni(ka.variants[vs[0]].N);
-    const u32 z = L.q5[N];
-    const bool bad = block_or(L.flag + 1, fold_writeback<NT>(ka, L, inc, N));   // (mfe_cells.hip: __syncthreads_or)
-    if (threadIdx.x == 0) fold_result(ka, w, vs, gout, z, bad);
 }
 
 template <int NM>
 static hipError_t launch_pair_nm(const KArgs &ka, const uint8_t *seqs, int W, float *gout, const int *mask,
-                                 hipStream_t stream) {
+                                 hipStream_t stream, int grid) {
     constexpr size_t lds = PLay<NM>::BYTES;
     auto k = mfe_pair_kernel<NWV * WAVE, NM>;
+    if (!ka.pairq) return hipErrorInvalidValue;
     // the carve addresses LDS from 0 (lds_at): no static LDS may precede the block
     hipError_t e = configure_dynamic_lds(k, lds, true);
     if (e != hipSuccess) return e;
+    // the workgroups resident at once (asked once per instantiation): more would
+    // only queue behind them for the same items
+    static const int resident = [&]() {
+        int nb = 0, dev = 0, cus = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void *>(k), NWV * WAVE, lds) !=
+                hipSuccess ||
+            hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+            return 0;
+        return nb * cus;
+    }();
+    if (resident <= 0) return hipErrorLaunchFailure;
+    const int items = W * ka.n_groups2;
+    if (items <= 0) return hipSuccess;
+    constexpr int GRID_MAX = 1 << 16;   // of ADX_PAIR_GRID: a workgroup past the items leaves at once
+    const int wgs = grid > 0 ? std::min(grid, GRID_MAX) : std::min(items, resident);
+    if (!ka.order) {   // with an order list order_kernel zeroed the counter
+        e = hipMemsetAsync(ka.pairq, 0, sizeof(int), stream);
+        if (e != hipSuccess) return e;
+    }
     static bool reported = false;
     if (!reported && std::getenv("ADX_OCC")) {   // diagnostic: resident workgroups per CU at this LDS size
         hipFuncAttributes fa;
@@ -1235,7 +1329,7 @@ static hipError_t launch_pair_nm(const KArgs &ka, const uint8_t *seqs, int W, fl
                      NWV, lds, fa.numRegs, nb);
     }
     reported = true;
-    hipLaunchKernelGGL(k, dim3(W * ka.n_groups2), dim3(NWV * WAVE), lds, stream, ka, ka.X, ka.T, seqs, W, gout, mask);
+    hipLaunchKernelGGL(k, dim3(wgs), dim3(NWV * WAVE), lds, stream, PairArgs{ka, ka.X, ka.T, seqs, W, gout, mask});
     return hipGetLastError();
 }
 
@@ -1245,10 +1339,10 @@ static hipError_t launch_pair_nm(const KArgs &ka, const uint8_t *seqs, int W, fl
 bool mfe_pair_covers(const KArgs &ka) { return ka.Nmax <= 100; }
 
 hipError_t launch_mfe_pair(const KArgs &ka, const uint8_t *seqs, int W, float *gout, const int *mask,
-                           hipStream_t stream) {
+                           hipStream_t stream, int grid) {
     static_assert(PLay<100>::BYTES <= 80 * 1024, "two 100-nt walkers per CU");
-    if (ka.Nmax <= 64) return launch_pair_nm<64>(ka, seqs, W, gout, mask, stream);
-    if (ka.Nmax <= 100) return launch_pair_nm<100>(ka, seqs, W, gout, mask, stream);
+    if (ka.Nmax <= 64) return launch_pair_nm<64>(ka, seqs, W, gout, mask, stream, grid);
+    if (ka.Nmax <= 100) return launch_pair_nm<100>(ka, seqs, W, gout, mask, stream, grid);
     return hipErrorInvalidValue;
 }
 
