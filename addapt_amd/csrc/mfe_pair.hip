@@ -16,7 +16,8 @@
 //      U(i, j) = min(qm1(i, j), U(i+1, j) + MLbase) (cell e1 takes U of row
 //      i+1 from the next lane), qm = min(split, U).  A refold runs only the
 //      rows it rewrites and one ghost row above them, whose restored qm stands
-//      in for its U (see F below)
+//      in for its U (see F below); a window of at most 32 rows runs one cell
+//      per lane, the two cells of a row on the two halves of the wave
 //   B  interior-loop partials of diagonals d and d+1, loop sizes u >= 2
 //      (inner spans <= d-3: final a step earlier), one lane-set over the
 //      pairable cells of both; every block wave folds its partial into the
@@ -584,6 +585,7 @@ __device__ __forceinline__ void load_list(const CP &L, int lane, int sl, int &PP
 // F's anchor and running values (the waves with a finalize lane-set)
 struct FRun {
     int ab;                           // the anchor: lane 0 of lane-set 0 is row ab (0: not chosen yet)
+    int pk;                           // the mode ab was chosen in: 1 packed (one wave, a cell per lane), 0 two cells per lane
     int fd;                           // the step the values below stand for (0, or a step this wave sat out: none)
     int oE0, oE1, oS1, oS2, oS3;      // uniform: off() of spans e0, e1, e0-1, e0-2, e0-3
     uint32_t mS, mM;                  // uniform: split slots e0 % 6, (e0 + 4) % 6 (bytes)
@@ -592,7 +594,143 @@ struct FRun {
     uint32_t fSi, fSi1, fUi, fUi1;    //   S[i], S[i+1], up[i], up[i+1],
     uint32_t fRq;                     //   the address of qm(i, i + 4) less 4 words,
     uint32_t fJ4, fSj, fQ1;           //   4 jA, the addresses of S[jA - 1] and qm1(i, jA - 1)
+                                      //   (packed: of the lane's own column j = jA | jA + 1)
+    uint32_t fH;                      //   packed: the lane's half as a ring-slot stride (0 | NP words, bytes)
 };
+
+// F packed (the finalize wave, a window of at most 32 rows): the cells of one
+// step side by side.  Lane l is row ab + (l & 31); lanes 0..31 finalize the
+// span-e0 cell (i, jA) of their row, lanes 32..63 the span-e1 cell (i, jA + 1) of
+// the same row, each from one read batch of its own cell's terms.  The per-lane
+// running values are those of finalize() taken at the lane's own column j (the
+// slow path adds the half to jA); the uniform ones are shared with the
+// two-cells-per-lane mode, and a half picks its spans' offsets from them.  Two
+// values cross the halves: qm1(i, jA), the upper half's qm1 predecessor, comes
+// from lane l - 32 in one v_permlane32_swap once the lower half has it, and
+// U(i + 1, jA + 1) from lower-half lane (l & 31) + 1 through F's ds_bpermute.
+// One lane-set, so no overlap lane: every lane of the window owns its cell.  The
+// window's last row is row R (no span-e1 cell) or the ghost (its U is the
+// restored qm) as in finalize(), and it sits on lane lr - ab <= 31, so the
+// upper half's last row never uses the neighbour it does not have (lane 32, or a
+// masked lane).  q1P, q1: the addresses of qm1(i, j - 1) and qm1(i, j).
+// (tests/test_finalize_packed_model.py restates the mapping and the addresses)
+template <int NM>
+__device__ __forceinline__ void finalize_packed(const CP &L, const FRun &f, const BUni &U, int N, int e0, int lane,
+                                                int mloF, int mhiF, u32 mlclosing, u32 mlbase, uint32_t q1P,
+                                                uint32_t q1 PSTAMP_PARAMS) {
+    constexpr uint32_t NP4 = uint32_t(NM + 2) * 4u;
+    const uint32_t aq = U.aq, ac = U.ac;
+    const bool hB = lane >= 32;
+    const int i = f.fI;
+    const uint32_t i4 = uint32_t(i) * 4u, iH = i4 + f.fH;
+    const int e = e0 + (hB ? 1 : 0);                 // the lane's span
+    const int j = int(f.fJ4 >> 2);                   // and column, i + e
+    const int oE = hB ? f.oE1 : f.oE0;               // off() of spans e, e-2, e-3
+    const int o2 = hB ? f.oS1 : f.oS2, o3 = hB ? f.oS2 : f.oS3;
+    const bool cell = j <= N;                        // row R has no span-e1 cell
+    const bool ghost = i == mhiF + 3;
+    const uint32_t qX = (aq - 4u) + uint32_t(oE) * 4u + i4;
+    const uint32_t pA = (lds_addr(L.part) + 2u * f.cW) + iH + f.fH;   // slot e & 3, both halves
+    const uint32_t uW = (lds_addr(L.colmin) + f.cW) + f.fH + f.fJ4;   // U(.., j) of span e
+    const uint32_t gq = f.fRq + (f.fJ4 - i4);                         // qm(i, j)
+    u32 init, cce, st, pq, ml, sp, up, p0, p1, v2, c2, v3, c3, v3b, c3b, gv;
+    uint32_t sjm, sj, uj, djm;
+    const uint32_t si = f.fSi, si1 = f.fSi1, ui = f.fUi, ui1 = f.fUi1;
+    {
+        const uint32_t mA = (lds_addr(L.mla) + f.mM + 4u) + iH;   // span e-2, row i + 1
+        const uint32_t sA = (lds_addr(L.mla) + f.mS) + iH;        // slot e % 6
+        // U(i + 1, jA) of span e0-1 (the lower half's; the upper half takes its U across the halves
+        // and reads the next column of the same slot for nothing)
+        const uint32_t uA = (lds_addr(L.colmin) + 3u * NP4 - f.cW) + f.fJ4;
+        asm volatile(
+            "ds_read_b32 %[init], %[qX]\n"
+            "ds_read_u8 %[cce], %[kX]\n"
+            "ds_read_b32 %[st], %[q1]\n"
+            "ds_read_b32 %[pq], %[q1P]\n"
+            "ds_read_b32 %[ml], %[mA]\n"
+            "ds_read_b32 %[sp], %[sA]\n"
+            "ds_read_b32 %[up], %[uA]\n"
+            "ds_read_b32 %[p0], %[pA]\n"
+            "ds_read_b32 %[p1], %[pA] offset:%[pst]\n"
+            "ds_read_b32 %[v2], %[q2]\n"
+            "ds_read_b32 %[v3], %[q3]\n"
+            "ds_read_b32 %[v3b], %[q3] offset:4\n"
+            "ds_read_u8 %[c2], %[k2]\n"
+            "ds_read_u8 %[c3], %[k3]\n"
+            "ds_read_u8 %[c3b], %[k3] offset:1\n"
+            // S, up, dn lie NP bytes apart (the carve): one address, j - 1 in S
+            "ds_read_u8 %[sjm], %[aSj] offset:0\n"
+            "ds_read_u8 %[sj], %[aSj] offset:1\n"
+            "ds_read_u8 %[uj], %[aSj] offset:%[ou]\n"
+            "ds_read_u8 %[djm], %[aSj] offset:%[od]\n"
+            "ds_read_b32 %[gv], %[gq]\n"
+            "s_waitcnt lgkmcnt(0)"
+            : [init] "=&v"(init), [cce] "=&v"(cce), [st] "=&v"(st), [pq] "=&v"(pq), [ml] "=&v"(ml), [sp] "=&v"(sp),
+              [up] "=&v"(up), [p0] "=&v"(p0), [p1] "=&v"(p1), [v2] "=&v"(v2), [v3] "=&v"(v3), [v3b] "=&v"(v3b),
+              [c2] "=&v"(c2), [c3] "=&v"(c3), [c3b] "=&v"(c3b), [sjm] "=&v"(sjm), [sj] "=&v"(sj), [uj] "=&v"(uj),
+              [djm] "=&v"(djm), [gv] "=&v"(gv)
+            : [qX] "v"(qX), [kX] "v"((ac - 1u) + uint32_t(oE) + uint32_t(i)), [q1] "v"(q1), [q1P] "v"(q1P), [mA] "v"(mA),
+              [sA] "v"(sA), [uA] "v"(uA), [pA] "v"(pA), [pst] "i"(NP4), [q2] "v"(aq + uint32_t(o2) * 4u + i4),
+              [q3] "v"(aq + uint32_t(o3) * 4u + i4), [k2] "v"(ac + uint32_t(o2) + uint32_t(i)),
+              [k3] "v"(ac + uint32_t(o3) + uint32_t(i)), [aSj] "v"(f.fSj), [ou] "i"(NM + 2 + 1),
+              [od] "i"(2 * (NM + 2)), [gq] "v"(gq)
+            : "memory");
+    }
+#ifdef ADX_STAMP_F
+    PSTAMP(11);   // F: the read batch
+#endif
+    const int ty = ptype(si, sj), t8 = ty * 8;
+    auto stk = [&](u32 v, u32 c) {   // inner pair with code c closing a stack with the cell's type
+        return padd(v, padd(L.ct[CT_INVMM + c], L.ct[CT_STK + t8 + ((int(c) * 41) >> 10)]));
+    };
+    // (i, j): stack inner (i+1, j-1) span e-2 [v2]; bulges (0,1) inner (i+1, j-2) [v3],
+    // (1,0) inner (i+2, j-1) [v3b], span e-3.  The lookups stay behind their conditions:
+    // taking all eight table entries in one round trip, needed or not, measured -0.3 %
+    // (profiles/fpack_ab.txt)
+    u32 iX = e >= 6 ? stk(v2, c2) : INF16;
+    if (e0 >= 6) {   // (e0 = 4: e < 7 on both halves)
+        const bool b7 = e >= 7;
+        iX = pmin(iX, b7 && djm >= 1 ? padd(stk(v3, c3), U.fs1) : INF16);
+        iX = pmin(iX, b7 && ui1 >= 1 ? padd(stk(v3b, c3b), U.fs1) : INF16);
+    }
+    const u32 mlcl = padd(mlclosing, L.dt[DT_MLS + rtype(ty) * 25 + sjm * 5 + si1]);
+    const u32 mmi = L.dt[DT_MMI + cce];
+    // the band's rows of the lane's span (Band::clo .. chi: i >= m_lo - 1 - e)
+    const bool in = cell && j >= mloF - 1 && i <= mhiF + 1;
+    auto st32 = [](uint32_t a, u32 v) { *lds_at<u32>(a) = v; };   // the batch's addresses serve the stores
+    const bool pairable = init != MARK16;
+    u32 c = pmin(init, pack2(int(p0), int(p1)));
+    c = pmin(c, iX);
+    c = pfin(pmin(c, padd(ml, mlcl)));
+    if (in && pairable) st32(qX, pfin(padd(c, mmi)));
+    const u32 cs = pairable ? padd(c, st) : INF16;
+    const bool pv = e >= 5 && uj >= 1;
+    // qm1 = min(c + stem, qm1(i, j - 1) + MLbase); restored outside the band
+    auto m1of = [&](u32 p) { return in ? pfin(pmin(cs, pv ? padd(p, mlbase) : INF16)) : st; };
+    u32 m1 = m1of(pq);
+    // the upper half's predecessor (i, jA) is the lower half's cell of the same row: the swap
+    // leaves pq in lanes 0..31 and puts lane l - 32's m1 into lanes 32..63
+    const auto sw = __builtin_amdgcn_permlane32_swap(pq, m1, false, false);
+    m1 = m1of(u32(sw[0]));
+    if (in) st32(q1, m1);
+#ifdef ADX_STAMP_F
+    PSTAMP(12);   // F: the cells' terms
+#endif
+    auto uof = [&](u32 below) { return ghost ? gv : (ui >= 1 ? pmin(m1, padd(below, mlbase)) : m1); };
+    // U of row i+1 in column jA+1 (span e0) is the lower half's value of the next row
+    const u32 UA1 = u32(__builtin_amdgcn_ds_bpermute(((lane & 31) + 1) * 4, int(uof(up))));
+    const u32 Uf = uof(hB ? UA1 : up);
+    if (cell) {
+        st32(uW, Uf);
+        st32(pA, u32(PINF));
+        st32(pA + NP4, u32(PINF));
+        if (e <= N - 3 && j >= mloF - 2 && i <= mhiF + 2)   // Band::qlo(e) .. qhi(e)
+            st32(gq, pfin(pmin(e >= 9 ? sp : INF16, Uf)));
+    }
+#ifdef ADX_STAMP_F
+    PSTAMP(13);   // F: U, the stores
+#endif
+}
 
 // F: finalize e0 = d-2 and e1 = d-1 on lane-set fls.  mloF, mhiF: the changed hull (a
 // fold from scratch is a refold whose hull clamps nowhere).  Lanes = rows i, from
@@ -621,6 +759,17 @@ struct FRun {
 // and the ring slots are uniform shift registers, the lane's column and its qm1
 // column base advance by adds, its row's bytes and qm base stay
 // (tests/test_finalize_anchor_model.py restates all of it).
+//
+// The mode is chosen with the anchor: a window that fits a half-wave
+// (lr - fr <= 31) runs packed on the finalize wave (finalize_packed above: anchor
+// max(1, lr - 31), lane-set 1 does not exist), any other as described here.  The
+// rule is a function of (fr, lr, the previous anchor and mode) alone: re-anchor
+// when there is no anchor, when fr falls below it or when the fit differs from
+// the mode, so a change of mode goes through the slow path like any re-anchor.
+// The window grows by two rows a step until it clamps and shrinks with R: at
+// most two changes a sweep after the first choice (packed, two cells per lane,
+// packed).  Both F waves evaluate the rule; the uniform running values serve
+// both modes.
 template <int NM, int fls>
 __device__ __forceinline__ void finalize(const CP &L, FRun &f, const BUni &U, int N, int d, int lane, int mloF,
                                          int mhiF, u32 mlclosing, u32 mlbase PSTAMP_PARAMS) {
@@ -631,21 +780,26 @@ __device__ __forceinline__ void finalize(const CP &L, FRun &f, const BUni &U, in
     const int R = N - e0;                                   // rows of span e0 (e1: R - 1)
     const int fr = max(1, mloF - 2 - e1);                   // Band::qlo(e1)
     const int lr = min(R, mhiF + 3);
-    if (e0 <= N - 1 && (f.ab == 0 || fr < f.ab)) {              // (re-)anchor: both F waves alike
-        f.ab = max(1, lr - (lr - fr < 64 ? 63 : 126));
+    const int fit = lr - fr <= 31 ? 1 : 0;                    // the window fits a half-wave: packed
+    if (e0 <= N - 1 && (f.ab == 0 || fr < f.ab || fit != f.pk)) {   // (re-)anchor: both F waves alike
+        f.pk = fit;
+        f.ab = max(1, lr - (fit ? 31 : (lr - fr < 64 ? 63 : 126)));
         f.fd = 0;
     }
-    if (e0 <= N - 1 && (fls == 0 || lr - f.ab > 63)) {        // lane-set 1: only past row ab + 63
+    if (e0 <= N - 1 && (fls == 0 || lr - f.ab > 63)) {        // lane-set 1: only past row ab + 63 (never packed)
         __builtin_amdgcn_s_setprio(PRIO_ROLE);
         constexpr uint32_t NP4 = uint32_t(NM + 2) * 4u;      // a ring slot, a partial half (bytes)
         const uint32_t aq = U.aq, ac = U.ac, aS = lds_addr(L.S);
         if (fls == 1 || f.fd != d) {   // the slow path: the closed forms at (ab, d); lane-set 1 (a block
                                      // wave, a few steps of a wide refold) keeps no state but ab
-            f.fI = f.ab + fls * 63 + lane;
+            const bool pk = fls == 0 && f.pk != 0;
+            const int hB = pk && lane >= 32 ? 1 : 0;           // packed: the upper half's cells are one span on
+            f.fI = f.ab + (pk ? (lane & 31) : fls * 63 + lane);
+            f.fH = hB ? NP4 : 0u;
             const int ic = min(f.fI, N);                       // rows past N are never active
             f.fSi = L.S[ic], f.fSi1 = L.S[ic + 1], f.fUi = L.up[ic], f.fUi1 = L.up[ic + 1];
             f.fRq = aqm + uint32_t(rowb(f.fI, N) - 4) * 4u;
-            const int jA = f.fI + e0;
+            const int jA = f.fI + e0 + hB;
             f.fJ4 = uint32_t(jA) * 4u;
             f.fSj = aS + uint32_t(jA - 1);
             f.fQ1 = aqm1 + uint32_t(colb(jA - 1) + f.fI - 1) * 4u;
@@ -661,6 +815,11 @@ __device__ __forceinline__ void finalize(const CP &L, FRun &f, const BUni &U, in
         const uint32_t i4 = uint32_t(i) * 4u;
         const uint32_t q1P = f.fQ1, q1A = q1P + (f.fJ4 - 20u), q1B = q1A + (f.fJ4 - 16u);   // colb(j+1) - colb(j) = j - 4
         if (i >= fr && i <= lr) {
+        bool pk = false;
+        if constexpr (fls == 0) pk = f.pk != 0;
+        if (pk) {
+            finalize_packed<NM>(L, f, U, N, e0, lane, mloF, mhiF, mlclosing, mlbase, q1P, q1A PSTAMP_ARGS);
+        } else {
         const bool own = lane < 63 || fls == 1 || lr - f.ab <= 63;   // the overlap lane writes nothing
         const bool rowB = i <= R - 1;
         const bool ghost = i == mhiF + 3;
@@ -818,6 +977,7 @@ __device__ __forceinline__ void finalize(const CP &L, FRun &f, const BUni &U, in
 #ifdef ADX_STAMP_F
         PSTAMP(13);   // F: U, the stores
 #endif
+        }
         }
 #ifdef ADX_STAMP_F
         {   // the sub-phase sums were advanced by the window's lanes only: every lane
