@@ -1184,6 +1184,32 @@ struct adx_ctx {
     double score_ms_total = 0.0;   // sum of the score-kernel launch durations of the last run
     double inside_ms_total = 0.0, outside_ms_total = 0.0;   // the same windows split (inside, outside)
     int score_launches = 0;
+    // The pick record (adx_record_begin): four of the trace's arrays kept on the
+    // device for the whole run, [max_steps x W] step-major, the walkers' sequences
+    // before its first step, and what the replay reads of the run-constant setup
+    struct Record {
+        bool on = false, broken = false;
+        int max_steps = 0, rows = 0, W = 0;
+        long long step0 = 0;   // the context's step index of row 0
+        DevBuf<double> cur;
+        DevBuf<int32_t> pos, out;
+        DevBuf<int8_t> base;
+        DevBuf<uint8_t> seq0, lower;
+        DevBuf<int> posmap;
+        void clear() {
+            on = broken = false;
+            max_steps = rows = W = 0;
+            cur.reset();
+            pos.reset();
+            out.reset();
+            base.reset();
+            seq0.reset();
+            lower.reset();
+            posmap.reset();
+        }
+        bool live() const { return on && !broken; }
+    } rec;
+    double pick_ms = 0.0, replay_ms = 0.0;   // the last adx_record_picks, from HIP events
 
     ~adx_ctx() {
         if (ev0) (void)hipEventDestroy(ev0);
@@ -1479,6 +1505,7 @@ extern "C" adx_status adx_walkers_init(adx_ctx *c, int W, const char *seqs, cons
     for (int w = 0; w < W; w++) mt_seed_host(seeds[w], &mt[size_t(w) * MT_WORDS]);
     c->W = W;
     c->step = 0;
+    if (c->rec.on) c->rec.broken = true;   // new sequences outside the log
     HIP_TRY(c->cur_seq.upload(codes.data(), codes.size(), pb.stream));
     HIP_TRY(c->mtA.upload(mt.data(), mt.size(), pb.stream));
     HIP_TRY(c->mtC.upload(mt.data(), mt.size(), pb.stream));
@@ -1535,6 +1562,11 @@ extern "C" adx_status adx_run_steps(adx_ctx *c, int steps, adx_trace *trace) {
     if (c->W <= 0) return fail(ADX_ESTATE, "adx_run_steps before adx_walkers_init");
     if (steps <= 0) return ADX_OK;
     Problem &pb = c->pb;
+    auto &rec = c->rec;
+    const bool recording = rec.live();
+    if (recording && steps > rec.max_steps - rec.rows)
+        return fail(ADX_ESTATE, "adx_run_steps: %d steps on top of the %d recorded exceed the record's max_steps %d",
+                    steps, rec.rows, rec.max_steps);
     StepArgs st{};
     st.cur_seq = c->cur_seq.p;
     st.cur_score = c->cur_score.p;
@@ -1577,24 +1609,34 @@ extern "C" adx_status adx_run_steps(adx_ctx *c, int steps, adx_trace *trace) {
     DevBuf<int8_t> tbase;
     DevBuf<double> ttemp, tprop, tcur, tu, tterms;
     const size_t R = size_t(steps) * W;
-    if (trace) {
+    if (recording) {   // the record's next rows; a trace reads these four back from them
+        const size_t r0 = size_t(rec.rows) * W;
+        st.tr_pos = rec.pos.p + r0;
+        st.tr_outcome = rec.out.p + r0;
+        st.tr_base = rec.base.p + r0;
+        st.tr_cur = rec.cur.p + r0;
+    } else if (trace) {
         HIP_TRY(tpos.alloc(R));
         HIP_TRY(tout.alloc(R));
         HIP_TRY(tbase.alloc(R));
-        HIP_TRY(ttemp.alloc(R));
-        HIP_TRY(tprop.alloc(R));
         HIP_TRY(tcur.alloc(R));
-        HIP_TRY(tu.alloc(R));
-        HIP_TRY(tterms.alloc(R * std::max(1, ntt)));
         st.tr_pos = tpos.p;
         st.tr_outcome = tout.p;
         st.tr_base = tbase.p;
+        st.tr_cur = tcur.p;
+    }
+    if (trace) {
+        HIP_TRY(ttemp.alloc(R));
+        HIP_TRY(tprop.alloc(R));
+        HIP_TRY(tu.alloc(R));
+        HIP_TRY(tterms.alloc(R * std::max(1, ntt)));
         st.tr_temp = ttemp.p;
         st.tr_prop = tprop.p;
-        st.tr_cur = tcur.p;
         st.tr_u = tu.p;
         st.tr_terms = ntt > 0 ? tterms.p : nullptr;
     }
+    // rows of a failed launch stay unwritten: the record counts as broken until the steps are in
+    if (recording) rec.broken = true;
     // events around every score window (the dominant kernels) for its average duration
     std::vector<hipEvent_t> evs(4 * size_t(steps));
     for (auto &e : evs) HIP_TRY(hipEventCreate(&e));
@@ -1632,21 +1674,25 @@ extern "C" adx_status adx_run_steps(adx_ctx *c, int steps, adx_trace *trace) {
     HIP_TRY(hipMemcpy(errs.data(), c->err.p, sizeof(int) * W, hipMemcpyDeviceToHost));
     if (trace) {
         std::vector<int8_t> b(R);
-        if (trace->position) HIP_TRY(hipMemcpy(trace->position, tpos.p, R * 4, hipMemcpyDeviceToHost));
-        if (trace->outcome) HIP_TRY(hipMemcpy(trace->outcome, tout.p, R * 4, hipMemcpyDeviceToHost));
+        if (trace->position) HIP_TRY(hipMemcpy(trace->position, st.tr_pos, R * 4, hipMemcpyDeviceToHost));
+        if (trace->outcome) HIP_TRY(hipMemcpy(trace->outcome, st.tr_outcome, R * 4, hipMemcpyDeviceToHost));
         if (trace->base) {
-            HIP_TRY(hipMemcpy(b.data(), tbase.p, R, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(b.data(), st.tr_base, R, hipMemcpyDeviceToHost));
             for (size_t k = 0; k < R; k++) trace->base[k] = b[k] >= 1 && b[k] <= 4 ? "ACGU"[b[k] - 1] : 'N';
         }
         if (trace->temperature) HIP_TRY(hipMemcpy(trace->temperature, ttemp.p, R * 8, hipMemcpyDeviceToHost));
         if (trace->proposed_score) HIP_TRY(hipMemcpy(trace->proposed_score, tprop.p, R * 8, hipMemcpyDeviceToHost));
-        if (trace->current_score) HIP_TRY(hipMemcpy(trace->current_score, tcur.p, R * 8, hipMemcpyDeviceToHost));
+        if (trace->current_score) HIP_TRY(hipMemcpy(trace->current_score, st.tr_cur, R * 8, hipMemcpyDeviceToHost));
         if (trace->random_threshold) HIP_TRY(hipMemcpy(trace->random_threshold, tu.p, R * 8, hipMemcpyDeviceToHost));
         if (trace->term_values && ntt > 0)
             HIP_TRY(hipMemcpy(trace->term_values, tterms.p, R * ntt * 8, hipMemcpyDeviceToHost));
     }
     for (int w = 0; w < W; w++)
         if (errs[w]) return fail(ADX_EMOVE, "walker %d: %s", w, move_error_text(errs[w]));
+    if (recording) {
+        rec.rows += steps;
+        rec.broken = false;
+    }
     return ADX_OK;
 }
 
@@ -1744,6 +1790,7 @@ extern "C" adx_status adx_walkers_export_on(adx_ctx *c, void *dev_seqs, void *de
 static hipError_t import_queue(adx_ctx *c, const void *dev_seqs, const void *dev_scores) {
     const size_t W = size_t(c->W), N = size_t(c->pb.Nraw);
     hipError_t e = hipSuccess;
+    if (c->rec.on) c->rec.broken = true;   // the configurations change outside the log
     if (dev_seqs) e = hipMemcpyAsync(c->cur_seq.p, dev_seqs, W * N, hipMemcpyDeviceToDevice, c->pb.stream);
     if (e == hipSuccess && dev_scores)
         e = hipMemcpyAsync(c->cur_score.p, dev_scores, W * sizeof(double), hipMemcpyDeviceToDevice, c->pb.stream);
@@ -1983,5 +2030,209 @@ extern "C" adx_status adx_score_batch(adx_ctx *c, int W, const char *seqs, doubl
     if (term_values && ntt > 0)
         HIP_TRY(hipMemcpy(term_values, dterms.p, sizeof(double) * W * ntt, hipMemcpyDeviceToHost));
     if (dG) HIP_TRY(hipMemcpy(dG, ddg.p, sizeof(float) * W * V, hipMemcpyDeviceToHost));
+    return ADX_OK;
+}
+
+// ================================================================== picks
+// (traj_pick.hip; the rule: traj_pick_core.hpp)
+namespace {
+
+#define MEM_TRY(expr)                                                                      \
+    do {                                                                                   \
+        hipError_t e_ = (expr);                                                            \
+        if (e_ == hipErrorOutOfMemory) {                                                   \
+            (void)hipGetLastError();                                                       \
+            return fail(ADX_ENOMEM, "%s: out of device memory", #expr);                    \
+        }                                                                                  \
+        if (e_ != hipSuccess)                                                              \
+            return fail(ADX_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_));         \
+    } while (0)
+
+constexpr int PICK_MAX_STEPS = 1 << 30;
+
+adx_status pick_args_ok(const char *who, int S, int window, int cap) {
+    if (window < 1)
+        return fail(ADX_EINVAL, "%s: window %d < 1 (cap must be at least ceil(steps / window))", who, window);
+    const int need = (S - 1) / window + 1;
+    if (cap < need)
+        return fail(ADX_EINVAL, "%s: cap %d too small: %d steps with window %d need cap >= %d", who, cap, S, window,
+                    need);
+    return ADX_OK;
+}
+
+// picks of W step-major device trajectories, chunk by chunk (keys / bad: scratch the caller frees)
+adx_status pick_device(const double *dscores, int W, int S, int window, int cap, DevBuf<uint64_t> &keys,
+                       DevBuf<int> &bad, int *dn, int32_t *dsteps, double *dpick, hipStream_t stream) {
+    const int chunk = traj_pick_chunk(S, W);
+    MEM_TRY(keys.alloc(traj_pick_key_words(S, chunk)));
+    MEM_TRY(bad.alloc(size_t(chunk)));
+    for (int w0 = 0; w0 < W; w0 += chunk)
+        HIP_TRY(launch_traj_pick(dscores, W, S, window, cap, w0, std::min(chunk, W - w0), keys.p, bad.p, dn, dsteps,
+                                 dpick, stream));
+    return ADX_OK;
+}
+
+struct Events3 {
+    hipEvent_t e[3] = {nullptr, nullptr, nullptr};
+    ~Events3() {
+        for (auto x : e)
+            if (x) (void)hipEventDestroy(x);
+    }
+};
+
+}  // namespace
+
+extern "C" adx_status adx_pick_scores(int device, int n_traj, int n_steps, const double *scores, int window, int cap,
+                                      int *n_picks, int32_t *steps) {
+    if (n_traj < 1 || n_steps < 1 || n_steps > PICK_MAX_STEPS || !scores || !n_picks || !steps)
+        return fail(ADX_EINVAL, "adx_pick_scores: bad argument");
+    adx_status s = pick_args_ok("adx_pick_scores", n_steps, window, cap);
+    if (s) return s;
+    Problem dev;   // the device checks and a stream
+    dev.device = device;
+    s = dev.init_device();
+    if (s) return s;
+    const size_t R = size_t(n_steps) * size_t(n_traj), O = size_t(n_traj) * size_t(cap);
+    DevBuf<double> dsc;
+    DevBuf<int> dn, bad;
+    DevBuf<int32_t> dst;
+    DevBuf<uint64_t> keys;
+    MEM_TRY(dsc.alloc(R));
+    MEM_TRY(dn.alloc(size_t(n_traj)));
+    MEM_TRY(dst.alloc(O));
+    HIP_TRY(hipMemcpyAsync(dsc.p, scores, R * sizeof(double), hipMemcpyHostToDevice, dev.stream));
+    HIP_TRY(hipMemsetAsync(dst.p, 0xff, O * sizeof(int32_t), dev.stream));
+    s = pick_device(dsc.p, n_traj, n_steps, window, cap, keys, bad, dn.p, dst.p, nullptr, dev.stream);
+    if (s) return s;
+    HIP_TRY(hipMemcpyAsync(n_picks, dn.p, sizeof(int) * size_t(n_traj), hipMemcpyDeviceToHost, dev.stream));
+    HIP_TRY(hipMemcpyAsync(steps, dst.p, O * sizeof(int32_t), hipMemcpyDeviceToHost, dev.stream));
+    HIP_TRY(hipStreamSynchronize(dev.stream));
+    return ADX_OK;
+}
+
+extern "C" adx_status adx_record_begin(adx_ctx *c, int max_steps) {
+    if (!c || max_steps < 1 || max_steps > PICK_MAX_STEPS) return fail(ADX_EINVAL, "adx_record_begin: bad argument");
+    if (c->W <= 0) return fail(ADX_ESTATE, "adx_record_begin before adx_walkers_init");
+    auto &rec = c->rec;
+    rec.clear();
+    const size_t W = size_t(c->W), N = size_t(c->pb.Nraw), R = size_t(max_steps) * W;
+    std::vector<int> posmap(N, -1);
+    for (size_t m = 0; m < c->mut.size(); m++) posmap[size_t(c->mut[m])] = int(m);
+    std::vector<uint8_t> lower(N);
+    for (size_t k = 0; k < N; k++) lower[k] = std::islower(static_cast<unsigned char>(c->templ[k])) ? 1 : 0;
+    hipError_t e = rec.cur.alloc(R);
+    if (e == hipSuccess) e = rec.pos.alloc(R);
+    if (e == hipSuccess) e = rec.out.alloc(R);
+    if (e == hipSuccess) e = rec.base.alloc(R);
+    if (e == hipSuccess) e = rec.seq0.alloc(W * N);
+    if (e == hipSuccess) e = rec.posmap.upload(posmap.data(), N, c->pb.stream);
+    if (e == hipSuccess) e = rec.lower.upload(lower.data(), N, c->pb.stream);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(rec.seq0.p, c->cur_seq.p, W * N, hipMemcpyDeviceToDevice, c->pb.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->pb.stream);   // posmap / lower are this call's locals
+    if (e != hipSuccess) {
+        rec.clear();
+        (void)hipGetLastError();
+        if (e == hipErrorOutOfMemory)
+            return fail(ADX_ENOMEM, "adx_record_begin: %d steps x %zu walkers x 17 bytes do not fit the device",
+                        max_steps, W);
+        return fail(ADX_EHIP, "adx_record_begin: %s", hipGetErrorString(e));
+    }
+    rec.on = true;
+    rec.max_steps = max_steps;
+    rec.W = c->W;
+    rec.step0 = c->step;
+    return ADX_OK;
+}
+
+extern "C" adx_status adx_record_end(adx_ctx *c) {
+    if (!c) return fail(ADX_EINVAL, "adx_record_end: null context");
+    HIP_TRY(hipStreamSynchronize(c->pb.stream));
+    c->rec.clear();
+    return ADX_OK;
+}
+
+extern "C" adx_status adx_record_picks(adx_ctx *c, int window, int cap, int *n_picks, int64_t *steps, double *scores,
+                                       char *seqs, int64_t *base_counts) {
+    if (!c || !n_picks || !steps) return fail(ADX_EINVAL, "adx_record_picks: null argument");
+    auto &rec = c->rec;
+    if (!rec.on) return fail(ADX_ESTATE, "adx_record_picks before adx_record_begin");
+    if (rec.broken)
+        return fail(ADX_ESTATE, "adx_record_picks: the record is broken (walkers initialised or imported during it, or "
+                                "a failed adx_run_steps); begin a new one");
+    if (rec.rows <= 0) return fail(ADX_ESTATE, "adx_record_picks: no step recorded yet");
+    Problem &pb = c->pb;
+    const int W = rec.W, S = rec.rows, N = pb.Nraw;
+    adx_status s = pick_args_ok("adx_record_picks", S, window, cap);
+    if (s) return s;
+    const size_t O = size_t(W) * size_t(cap);
+    DevBuf<int> dn, bad;
+    DevBuf<int32_t> dst;
+    DevBuf<double> dps;
+    DevBuf<char> dseq;
+    DevBuf<unsigned long long> dcnt;
+    DevBuf<uint64_t> keys;
+    MEM_TRY(dn.alloc(size_t(W)));
+    MEM_TRY(dst.alloc(O));
+    MEM_TRY(dps.alloc(O));
+    HIP_TRY(hipMemsetAsync(dst.p, 0xff, O * sizeof(int32_t), pb.stream));
+    HIP_TRY(hipMemsetAsync(dps.p, 0, O * sizeof(double), pb.stream));
+    if (seqs) {
+        MEM_TRY(dseq.alloc(O * size_t(N)));
+        HIP_TRY(hipMemsetAsync(dseq.p, 0, O * size_t(N), pb.stream));
+    }
+    if (base_counts) {
+        MEM_TRY(dcnt.alloc(size_t(N) * 4));
+        HIP_TRY(hipMemsetAsync(dcnt.p, 0, size_t(N) * 4 * sizeof(unsigned long long), pb.stream));
+    }
+    Events3 ev;
+    for (auto &x : ev.e) HIP_TRY(hipEventCreate(&x));
+    HIP_TRY(hipEventRecord(ev.e[0], pb.stream));
+    s = pick_device(rec.cur.p, W, S, window, cap, keys, bad, dn.p, dst.p, dps.p, pb.stream);
+    if (s) return s;
+    HIP_TRY(hipEventRecord(ev.e[1], pb.stream));
+    if (seqs || base_counts) {
+        ReplayArgs a{};
+        a.seq0 = rec.seq0.p;
+        a.pos = rec.pos.p;
+        a.base = rec.base.p;
+        a.outcome = rec.out.p;
+        a.W = W;
+        a.N = N;
+        a.rows = S;
+        a.posmap = rec.posmap.p;
+        a.clo_off = c->d_clo_off.p;
+        a.clo_pos = c->d_clo_pos.p;
+        a.clo_par = c->d_clo_par.p;
+        a.lower = rec.lower.p;
+        a.n_picks = dn.p;
+        a.steps = dst.p;
+        a.cap = cap;
+        a.seqs = dseq.p;
+        a.counts = dcnt.p;
+        HIP_TRY(launch_traj_replay(a, pb.stream));
+    }
+    HIP_TRY(hipEventRecord(ev.e[2], pb.stream));
+    std::vector<int32_t> rows(O);
+    HIP_TRY(hipMemcpyAsync(n_picks, dn.p, sizeof(int) * size_t(W), hipMemcpyDeviceToHost, pb.stream));
+    HIP_TRY(hipMemcpyAsync(rows.data(), dst.p, O * sizeof(int32_t), hipMemcpyDeviceToHost, pb.stream));
+    if (scores) HIP_TRY(hipMemcpyAsync(scores, dps.p, O * sizeof(double), hipMemcpyDeviceToHost, pb.stream));
+    if (seqs) HIP_TRY(hipMemcpyAsync(seqs, dseq.p, O * size_t(N), hipMemcpyDeviceToHost, pb.stream));
+    if (base_counts)
+        HIP_TRY(hipMemcpyAsync(base_counts, dcnt.p, size_t(N) * 4 * sizeof(int64_t), hipMemcpyDeviceToHost, pb.stream));
+    HIP_TRY(hipStreamSynchronize(pb.stream));
+    for (size_t k = 0; k < O; k++) steps[k] = rows[k] < 0 ? -1 : rec.step0 + rows[k];
+    float a = 0.f, b = 0.f;
+    HIP_TRY(hipEventElapsedTime(&a, ev.e[0], ev.e[1]));
+    HIP_TRY(hipEventElapsedTime(&b, ev.e[1], ev.e[2]));
+    c->pick_ms = a;
+    c->replay_ms = b;
+    return ADX_OK;
+}
+
+extern "C" adx_status adx_last_pick_ms(const adx_ctx *c, double *pick_ms, double *replay_ms) {
+    if (!c || !pick_ms || !replay_ms) return fail(ADX_EINVAL, "adx_last_pick_ms: null argument");
+    *pick_ms = c->pick_ms;
+    *replay_ms = c->replay_ms;
     return ADX_OK;
 }

@@ -245,7 +245,9 @@ struct StepArgs {
     long long step0;            // global step index of the first step of this launch
     int nsteps;
     int W;
-    // optional trace (nullptr when off), step-major [s * W + w]
+    // optional trace (tr_pos null: off), step-major [s * W + w].  tr_pos, tr_base,
+    // tr_outcome and tr_cur go together (the pick record keeps these four);
+    // tr_temp, tr_prop, tr_u and tr_terms may each be null on their own
     int32_t *tr_pos;
     int8_t *tr_base;
     int32_t *tr_outcome;

@@ -120,6 +120,34 @@ hipError_t launch_outside_m(const KArgs &ka, const uint8_t *seqs, int W, const i
 hipError_t launch_combine(const KArgs &ka, int W, const int *mask, double *scores, double *terms,
                           hipStream_t stream);
 
+// ---- traj_pick.hip: each trajectory's peaks (traj_pick_core.hpp) and the sequences at them.
+// Picking runs on chunks of trajectories [w0, w0 + nw) so that the trajectory-major
+// copy of their keys stays bounded: keys = traj_pick_key_words(S, chunk) uint64,
+// bad = chunk ints.  scores: S * W doubles, step-major; n_picks[W] (-1: a non-finite
+// score), steps[W * cap] ascending, pick_scores[W * cap] optional; the caller
+// checks window >= 1 and cap >= ceil(S / window).
+int traj_pick_chunk(int S, int n_traj);
+size_t traj_pick_key_words(int S, int chunk);
+hipError_t launch_traj_pick(const double *scores, int W, int S, int window, int cap, int w0, int nw, uint64_t *keys,
+                            int *bad, int *n_picks, int32_t *steps, double *pick_scores, hipStream_t stream);
+struct ReplayArgs {
+    const uint8_t *seq0;        // W * N codes: the walkers' sequences before the first recorded step
+    const int32_t *pos;         // the record, step-major [r * W + w]: freely mutable position chosen,
+    const int8_t *base;         //   base code chosen,
+    const int32_t *outcome;     //   outcome
+    int W, N, rows;             // rows recorded
+    const int *posmap;          // [N] position -> index into the closure lists (-1: not freely mutable)
+    const int *clo_off, *clo_pos;
+    const uint8_t *clo_par;
+    const uint8_t *lower;       // [N] 1: the template's base is lower case (frozen)
+    const int *n_picks;         // [W]
+    const int32_t *steps;       // [W * cap] ascending record rows
+    int cap;
+    char *seqs;                 // [W * cap * N] the sequence at each pick (optional)
+    unsigned long long *counts; // [N * 4] A, C, G, U over all picks, added to (optional)
+};
+hipError_t launch_traj_replay(const ReplayArgs &a, hipStream_t stream);
+
 // ---- mc_step.hip
 hipError_t launch_steps(const KArgs &ka, const StepArgs &st, hipStream_t stream, hipEvent_t *evs);
 hipError_t launch_rescore(const KArgs &ka, const StepArgs &st, double *tv, hipStream_t stream);

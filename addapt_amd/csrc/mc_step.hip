@@ -270,9 +270,9 @@ __device__ Accepted accept_walker(const StepArgs &st, const KArgs &kc, bool comb
         if (st.tr_pos) {
             const size_t r = size_t(s) * st.W + w;
             st.tr_outcome[r] = outcome;
-            st.tr_prop[r] = changed ? prop : __builtin_nan("");
+            if (st.tr_prop) st.tr_prop[r] = changed ? prop : __builtin_nan("");
             st.tr_cur[r] = acc ? prop : in.cs;
-            st.tr_u[r] = changed ? in.u : __builtin_nan("");
+            if (st.tr_u) st.tr_u[r] = changed ? in.u : __builtin_nan("");
             if (!changed && st.tr_terms)
                 for (int k = 0; k < nt_tot; k++) st.tr_terms[r * nt_tot + k] = __builtin_nan("");
         }
@@ -391,7 +391,7 @@ __device__ Proposed propose_walker(const StepArgs &st, long long step, int s, in
             const size_t r = size_t(s) * st.W + w;
             st.tr_pos[r] = st.mut[pick];
             st.tr_base[r] = int8_t(bcode);
-            st.tr_temp[r] = T;
+            if (st.tr_temp) st.tr_temp[r] = T;
         }
     }
     out.scored = e == 0 && changed;

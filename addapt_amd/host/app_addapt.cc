@@ -3,7 +3,9 @@
 //
 //   addapt <config>... [-n <num>] [-T <schedule>] [-r <seed>] [-o <path>]
 //                      [-i <steps>] [--walkers <W>] [--gpu <id>] [--params <file>]
-//                      [--reference-loop]
+//                      [--reference-loop] [--picks <path>] [--pick-window <steps>]
+#include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <iostream>
@@ -38,6 +40,12 @@ static const char USAGE[] =
     "  --walkers <W>                          [default: 1]\n"
     "    Run W independent walkers (seeds r .. r+W-1) on the GPU at once and write\n"
     "    their final sequences and scores to the output instead of a trajectory.\n"
+    "  --picks <path>\n"
+    "    With --walkers: record every walker's trajectory on the GPU and write the\n"
+    "    peaks of each (scores at or above the trajectory's 75th percentile, best\n"
+    "    first, at least the pick window apart) with the sequences there.\n"
+    "  --pick-window <steps>                  [default: 500]\n"
+    "    The least distance between two picks of one trajectory.\n"
     "  --gpu <id>                             [default: 0]\n"
     "  --params <file>  Energy parameters (ViennaRNA 2.0 format).\n"
     "  --reference-loop  Run the reference's single-walker loop (one GPU fold call\n"
@@ -45,10 +53,44 @@ static const char USAGE[] =
     "  --version\n"
     "  -h, --help\n";
 
+// The picks of a batched run: the summary the reference's pick_seqs prints
+// (number of picks, best, worst, mean and sample standard deviation of their
+// scores) as '#' lines, then one row per pick.
+static void write_picks(const std::string &path, const BatchResult &res, const std::vector<uint32_t> &seeds) {
+    FILE *f = std::fopen(path.c_str(), "w");
+    if (!f) throw std::string("couldn't open '" + path + "' for writing");
+    size_t n = 0;
+    double best = 0, worst = 0, sum = 0;
+    for (auto &r : res)
+        for (auto &p : r.picks) {
+            best = n ? std::max(best, p.score) : p.score;
+            worst = n ? std::min(worst, p.score) : p.score;
+            sum += p.score;
+            n++;
+        }
+    if (n == 0) {
+        std::fprintf(f, "# No picks made\n");
+    } else {
+        const double mean = sum / double(n);
+        double ss = 0;
+        for (auto &r : res)
+            for (auto &p : r.picks) ss += (p.score - mean) * (p.score - mean);
+        const double sd = n > 1 ? std::sqrt(ss / double(n - 1)) : std::nan("");
+        std::fprintf(f, "# Num Picks: %zu\n# Best Score: %.4f\n# Worst Score: %.4f\n# Average Score: %.4f \xc2\xb1 %.4f\n",
+                     n, best, worst, mean, sd);
+    }
+    std::fprintf(f, "walker\tseed\tstep\tscore\tseq\n");
+    for (auto &r : res)
+        for (auto &p : r.picks)
+            std::fprintf(f, "%d\t%u\t%lld\t%.17g\t%s\n", p.walker, seeds[size_t(p.walker)], (long long)p.step, p.score,
+                         p.seq.c_str());
+    std::fclose(f);
+}
+
 int main(int argc, char **argv) {
     std::vector<std::string> configs;
-    std::string temp, out = "traj.tsv", params;
-    int num = 100, interval = 1, walkers = 1, gpu = 0;
+    std::string temp, out = "traj.tsv", params, picks;
+    int num = 100, interval = 1, walkers = 1, gpu = 0, pick_window = 500;
     unsigned long seed = 0;
     bool ref_loop = false;
     try {
@@ -66,6 +108,8 @@ int main(int argc, char **argv) {
             else if (a == "-o" || a == "--output") out = val("--output");
             else if (a == "-i" || a == "--output-interval") interval = std::stoi(val("--output-interval"));
             else if (a == "--walkers") walkers = std::stoi(val("--walkers"));
+            else if (a == "--picks") picks = val("--picks");
+            else if (a == "--pick-window") pick_window = std::stoi(val("--pick-window"));
             else if (a == "--gpu") gpu = std::stoi(val("--gpu"));
             else if (a == "--params") params = val("--params");
             else if (a == "--reference-loop") ref_loop = true;
@@ -76,6 +120,8 @@ int main(int argc, char **argv) {
             std::cerr << USAGE;
             return 1;
         }
+        if (!picks.empty() && walkers <= 1) throw std::string("--picks needs --walkers <W> with W > 1");
+        if (!picks.empty() && pick_window < 1) throw std::string("--pick-window must be at least 1");
         if (!params.empty()) set_parameter_file(params);
         DevicePtr device = device_from_yaml(configs);
         ScoreFunctionPtr sf = scorefxn_from_yaml(configs);
@@ -88,7 +134,7 @@ int main(int argc, char **argv) {
         if (walkers > 1) {
             std::vector<uint32_t> seeds(walkers);
             for (int w = 0; w < walkers; w++) seeds[w] = uint32_t(seed + w);
-            auto res = mc->apply_batch(device, seeds, gpu);
+            auto res = mc->apply_batch(device, seeds, gpu, picks.empty() ? 0 : pick_window);
             FILE *f = std::fopen(out.c_str(), "w");
             if (!f) throw std::string("couldn't open '" + out + "' for writing");
             std::fprintf(f, "walker\tseed\tscore\treject\taccept_worsened\taccept_unchanged\taccept_improved\tseq\n");
@@ -100,6 +146,7 @@ int main(int argc, char **argv) {
                              res[w].device->seq().c_str());
             }
             std::fclose(f);
+            if (!picks.empty()) write_picks(picks, res, seeds);
             return 0;
         }
         *mc += std::make_shared<ProgressReporter>();

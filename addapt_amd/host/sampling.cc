@@ -251,8 +251,9 @@ void build_setup(const MonteCarlo &mc, DeviceConstPtr device, int g, EngineSetup
 }
 }  // namespace
 
-std::vector<WalkerResult> MonteCarlo::apply_batch(DevicePtr device, const std::vector<uint32_t> &seeds, int g) const {
+BatchResult MonteCarlo::apply_batch(DevicePtr device, const std::vector<uint32_t> &seeds, int g, int pick_window) const {
     if (!gpu_expressible()) throw string("apply_batch: the score function / moves / thermostat are not GPU-expressible");
+    if (pick_window < 0) throw string("apply_batch: negative pick window");
     EngineSetup e;
     build_setup(*this, device, g, e);
     adx_ctx *raw = nullptr;
@@ -260,13 +261,32 @@ std::vector<WalkerResult> MonteCarlo::apply_batch(DevicePtr device, const std::v
     gpu::CtxPtr ctx(raw);
     const int W = int(seeds.size());
     gpu::check(adx_walkers_init(ctx.get(), W, nullptr, seeds.data()));
+    const bool picking = pick_window > 0 && steps_ > 0;
+    if (picking) gpu::check(adx_record_begin(ctx.get(), steps_));
     if (steps_ > 0) gpu::check(adx_run_steps(ctx.get(), steps_, nullptr));
     const size_t N = e.seq.size();
     std::vector<char> seqs(N * W);
     std::vector<double> scores(W);
     std::vector<int64_t> cnt(4 * size_t(W));
     gpu::check(adx_walkers_download(ctx.get(), seqs.data(), scores.data(), cnt.data()));
-    std::vector<WalkerResult> out(W);
+    BatchResult out;
+    out.resize(W);
+    if (picking) {
+        const size_t cap = size_t((steps_ - 1) / pick_window + 1);
+        std::vector<int> n(W);
+        std::vector<int64_t> psteps(cap * W);
+        std::vector<double> pscores(cap * W);
+        std::vector<char> pseqs(cap * W * N);
+        out.base_counts.assign(4 * N, 0);
+        gpu::check(adx_record_picks(ctx.get(), pick_window, int(cap), n.data(), psteps.data(), pscores.data(),
+                                    pseqs.data(), out.base_counts.data()));
+        gpu::check(adx_record_end(ctx.get()));
+        for (int w = 0; w < W; w++)
+            for (int k = 0; k < n[w]; k++) {   // n[w] = -1 (a non-finite score): no picks
+                const size_t o = size_t(w) * cap + k;
+                out[w].picks.push_back(Pick{w, psteps[o], pscores[o], string(&pseqs[o * N], N)});
+            }
+    }
     for (int w = 0; w < W; w++) {
         out[w].device = device->copy();
         for (size_t k = 0; k < N; k++) out[w].device->mutate(int(k), seqs[size_t(w) * N + k]);

@@ -87,6 +87,7 @@ EXPORTS = [
     "adx_last_sample_ms",
     "adx_fold_ensemble_structures", "adx_ensemble_structures_batch", "adx_walkers_ensemble_structures",
     "adx_last_ensemble_ms",
+    "adx_pick_scores", "adx_record_begin", "adx_record_end", "adx_record_picks", "adx_last_pick_ms",
 ]
 
 _lib = None
@@ -159,6 +160,13 @@ def lib():
                                      C.POINTER(C.c_double)]
         L.adx_variant_desc.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int),
                                        C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.adx_pick_scores.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int,
+                                      C.POINTER(C.c_int), C.POINTER(C.c_int32)]
+        L.adx_record_begin.argtypes = [C.c_void_p, C.c_int]
+        L.adx_record_end.argtypes = [C.c_void_p]
+        L.adx_record_picks.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int64),
+                                       C.POINTER(C.c_double), C.c_char_p, C.POINTER(C.c_int64)]
+        L.adx_last_pick_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         _lib = L
     return _lib
 
@@ -179,6 +187,26 @@ def kT():
 def theo_energy(kd_uM=0.32):
     """kT * ln(Kd / 1 M) -- the bonus scoring.cc:91-99 passes to vrna_sc_add_hi_motif."""
     return kT() * math.log(kd_uM / 1e6)
+
+
+def pick_scores(scores, window, cap=None, device=0):
+    """The peaks of trajectories given as a (steps, trajectories) float64 array
+    (adx_pick_scores): a list per trajectory of its picked steps, ascending, or
+    None for a trajectory with a non-finite score.  Each trajectory's threshold
+    is its 75th percentile; picks are at least `window` steps apart.  cap: the
+    per-trajectory capacity passed down (default: the least that always fits)."""
+    sc = np.ascontiguousarray(scores, np.float64)
+    if sc.ndim != 2:
+        raise ValueError("pick_scores: scores must be (steps, trajectories)")
+    S, W = sc.shape
+    if cap is None:
+        cap = -(-S // window) if window >= 1 else 1
+    n = np.zeros(max(W, 1), np.int32)
+    st = np.zeros(max(W * cap, 1), np.int32)
+    _check(lib().adx_pick_scores(device, W, S, sc.ctypes.data_as(C.POINTER(C.c_double)), window, cap,
+                                 n.ctypes.data_as(C.POINTER(C.c_int)), st.ctypes.data_as(C.POINTER(C.c_int32))))
+    st = st[:W * cap].reshape(W, cap)
+    return [None if n[w] < 0 else [int(x) for x in st[w, :n[w]]] for w in range(W)]
 
 
 class Params:
@@ -326,6 +354,7 @@ class Engine:
         _check(lib().adx_ctx_info(self.ptr, C.byref(self.info)))
         self.n_terms_total = len(terms) * max(1, len(ctx))
         self.W = 0
+        self._rec_rows = None   # steps in the pick record (None: no record)
 
     def __del__(self):
         if getattr(self, "ptr", None) and _lib is not None:
@@ -478,6 +507,8 @@ class Engine:
                        out["random_threshold"].ctypes.data_as(C.POINTER(C.c_double)),
                        out["term_values"].ctypes.data_as(C.POINTER(C.c_double)))
         _check(lib().adx_run_steps(self.ptr, steps, C.byref(tr) if tr is not None else None))
+        if self._rec_rows is not None:
+            self._rec_rows += max(0, steps)
         if trace:
             out["base"] = base.raw[:steps * self.W].decode()
             for k in ("position", "outcome", "temperature", "proposed_score", "current_score",
@@ -485,6 +516,49 @@ class Engine:
                 out[k] = out[k].reshape(steps, self.W)
             out["term_values"] = out["term_values"].reshape(steps, self.W, -1)[:, :, :self.n_terms_total]
         return out
+
+    def record(self, max_steps):
+        """Start the pick record (adx_record_begin): the following run_steps calls,
+        up to max_steps steps in all, keep each step's score and move on the device."""
+        _check(lib().adx_record_begin(self.ptr, max_steps))
+        self._rec_rows = 0
+
+    def record_end(self):
+        _check(lib().adx_record_end(self.ptr))
+        self._rec_rows = None
+
+    def picks(self, window, cap=None):
+        """(picks, base_counts) of the steps recorded so far (adx_record_picks):
+        per walker a list of (step, score, sequence) in ascending step order (None
+        for a walker whose recorded scores are not all finite), step being the
+        engine's global 0-based step index; base_counts is the (N, 4) int64
+        histogram of A, C, G, U over all walkers' picked sequences."""
+        W, N = self.W, self.N
+        if cap is None:
+            cap = max(1, -(-(self._rec_rows or 0) // window)) if window >= 1 else 1
+        n = np.zeros(max(W, 1), np.int32)
+        st = np.zeros(max(W * cap, 1), np.int64)
+        sc = np.zeros(max(W * cap, 1), np.float64)
+        buf = C.create_string_buffer(W * cap * N + 1)
+        cnt = np.zeros((N, 4), np.int64)
+        _check(lib().adx_record_picks(self.ptr, window, cap, n.ctypes.data_as(C.POINTER(C.c_int)),
+                                      st.ctypes.data_as(C.POINTER(C.c_int64)), sc.ctypes.data_as(C.POINTER(C.c_double)),
+                                      buf, cnt.ctypes.data_as(C.POINTER(C.c_int64))))
+        raw = buf.raw
+        out = []
+        for w in range(W):
+            if n[w] < 0:
+                out.append(None)
+                continue
+            out.append([(int(st[w * cap + k]), float(sc[w * cap + k]),
+                         raw[(w * cap + k) * N:(w * cap + k + 1) * N].decode()) for k in range(n[w])])
+        return out, cnt
+
+    def last_pick_ms(self):
+        """(picking kernels ms, replay kernel ms) of the last picks() call, from HIP events."""
+        a, b = C.c_double(), C.c_double()
+        _check(lib().adx_last_pick_ms(self.ptr, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def last_kernel_ms(self):
         ms = C.c_double()

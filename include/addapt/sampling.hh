@@ -144,11 +144,28 @@ private:
     std::ofstream tsv_;
 };
 
+/// one peak of a walker's trajectory (what the reference's pick_seqs script
+/// takes from a trajectory file): the 0-based step, the current score after
+/// it and the sequence then
+struct Pick {
+    int walker;
+    int64_t step;
+    double score;
+    std::string seq;
+};
+
 /// one walker's result of a batched run
 struct WalkerResult {
     DevicePtr device;
     double score;
     std::map<OutcomeEnum, long long> outcome_counters;
+    std::vector<Pick> picks;   ///< ascending steps; empty without a pick window
+};
+
+/// the walkers' results; with a pick window also how often A, C, G, U stand at
+/// each position over all walkers' picks (base_counts[4 * position + base])
+struct BatchResult : std::vector<WalkerResult> {
+    std::vector<int64_t> base_counts;
 };
 
 class MonteCarlo {
@@ -159,9 +176,12 @@ public:
     /// mt19937(seed): the fused GPU engine when the setup is built-in, else
     /// the reference loop
     DevicePtr apply(DevicePtr device, uint32_t seed) const;
-    /// W independent walkers (seeds[w]) on one GPU; reporters are not called
-    std::vector<WalkerResult> apply_batch(DevicePtr device, const std::vector<uint32_t> &seeds,
-                                          int gpu = 0) const;
+    /// W independent walkers (seeds[w]) on one GPU; reporters are not called.
+    /// pick_window > 0: each walker's trajectory is recorded on the GPU and its
+    /// peaks (threshold: the trajectory's 75th percentile; at least pick_window
+    /// steps apart) come back as WalkerResult::picks
+    BatchResult apply_batch(DevicePtr device, const std::vector<uint32_t> &seeds, int gpu = 0,
+                            int pick_window = 0) const;
     /// true if the fused GPU engine can run this setup
     bool gpu_expressible() const;
 

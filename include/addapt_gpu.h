@@ -362,6 +362,56 @@ adx_status adx_walkers_ensemble_structures(adx_ctx *ctx, int condition, int cont
  * the outside pass and the structure kernel. */
 adx_status adx_last_ensemble_ms(const adx_ctx *ctx, double *bppm_ms, double *struct_ms);
 
+/* ------------------------------------------------------------------------
+ * Picking each trajectory's best steps on the device (what the reference's
+ * pick_seqs script does with a trajectory file).  For one trajectory of S
+ * scores c[0..S) (c[r] = the current score after step r) and a window >= 1:
+ *   T      the 75th percentile of c (linear interpolation, numpy's default)
+ *   peaks  repeat: of the steps not yet blocked take the largest score (the
+ *          lowest step among equals); stop when none is left or it is not
+ *          >= T; else record it and block [max(i - window, 0), min(i + window, S))
+ * so picks are at least `window` steps apart and there are at most
+ * ceil(S / window) of them.  A trajectory with a NaN or an infinity is not
+ * picked: its count is -1.
+ * ---------------------------------------------------------------------- */
+
+/* Stateless: pick from caller-supplied trajectories (scores = n_steps * n_traj
+ * doubles, step-major: scores[r * n_traj + w]).  n_picks[n_traj] (-1:
+ * non-finite scores); steps = n_traj * cap int32, ascending, the first
+ * n_picks[w] of trajectory w's cap valid.  cap < ceil(n_steps / window) or
+ * window < 1: ADX_EINVAL naming the needed cap. */
+adx_status adx_pick_scores(int device, int n_traj, int n_steps, const double *scores, int window,
+                           int cap, int *n_picks, int32_t *steps);
+
+/* The pick record: from adx_record_begin on, consecutive adx_run_steps calls
+ * keep each step's current score and move (17 bytes per walker and step) on
+ * the device, up to max_steps steps in all; a call that would exceed
+ * max_steps returns ADX_ESTATE before it launches anything (the walkers are
+ * untouched).  adx_record_begin allocates and snapshots the walkers'
+ * sequences (ADX_ENOMEM leaves no record and nothing allocated; ADX_ESTATE
+ * before adx_walkers_init; a second begin starts over).  adx_walkers_init and
+ * adx_walkers_import* during a record change sequences outside the log, and a
+ * failed adx_run_steps leaves rows unwritten: either marks the record broken
+ * (adx_record_picks: ADX_ESTATE) until the next adx_record_begin.  Rescoring
+ * and the structure calls do not disturb it.  adx_record_end frees it. */
+adx_status adx_record_begin(adx_ctx *ctx, int max_steps);
+adx_status adx_record_end(adx_ctx *ctx);
+/* Picks of the steps recorded so far (may be called more than once, with
+ * different windows).  Per walker w, n_picks[w] picks (-1: non-finite scores)
+ * in ascending step order, the first n_picks[w] of its cap entries valid:
+ * steps[W * cap] the context's global 0-based step index of each pick;
+ * scores[W * cap] the current score there; seqs = W * cap * N chars, the
+ * walker's sequence after that step (as adx_walkers_download writes it);
+ * base_counts = N * 4 int64, how often A, C, G, U stand at each position over
+ * all walkers' picks.  scores, seqs and base_counts are optional (NULL).
+ * cap < ceil(recorded steps / window) or window < 1: ADX_EINVAL naming the
+ * needed cap; before adx_record_begin or with nothing recorded: ADX_ESTATE. */
+adx_status adx_record_picks(adx_ctx *ctx, int window, int cap, int *n_picks, int64_t *steps,
+                            double *scores, char *seqs, int64_t *base_counts);
+/* Device time (ms, HIP events) of the context's last adx_record_picks: the
+ * picking kernels and the replay kernel. */
+adx_status adx_last_pick_ms(const adx_ctx *ctx, double *pick_ms, double *replay_ms);
+
 /* Variant v of the score: which (context, condition, macrostate or -1). */
 adx_status adx_variant_desc(const adx_ctx *ctx, int v, int *context, int *condition,
                             int *macrostate);
