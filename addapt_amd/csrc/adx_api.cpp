@@ -20,6 +20,7 @@
 #include "dev_types.hpp"
 #include "energy.hpp"
 #include "launch.hpp"
+#include "traj_autocorr_core.hpp"
 
 using namespace adx;
 
@@ -1210,6 +1211,7 @@ struct adx_ctx {
         bool live() const { return on && !broken; }
     } rec;
     double pick_ms = 0.0, replay_ms = 0.0;   // the last adx_record_picks, from HIP events
+    double ac_pack_ms = 0.0, ac_lag_ms = 0.0;   // the last adx_record_autocorr, from HIP events
 
     ~adx_ctx() {
         if (ev0) (void)hipEventDestroy(ev0);
@@ -2234,5 +2236,190 @@ extern "C" adx_status adx_last_pick_ms(const adx_ctx *c, double *pick_ms, double
     if (!c || !pick_ms || !replay_ms) return fail(ADX_EINVAL, "adx_last_pick_ms: null argument");
     *pick_ms = c->pick_ms;
     *replay_ms = c->replay_ms;
+    return ADX_OK;
+}
+
+// ================================================================== autocorrelation
+// (traj_autocorr.hip; the quantity and the correlation-time rule: traj_autocorr_core.hpp)
+namespace {
+
+adx_status autocorr_args_ok(const char *who, int rows, int max_lag, int discard) {
+    if (discard < 0 || discard >= rows)
+        return fail(ADX_EINVAL, "%s: discard %d outside 0..%d (%d steps)", who, discard, rows - 1, rows);
+    const int kept = rows - discard;
+    if (max_lag < 0 || max_lag > kept - 1)
+        return fail(ADX_EINVAL, "%s: max_lag %d outside 0..%d: %d kept steps allow a lag of at most %d", who, max_lag,
+                    kept - 1, kept, kept - 1);
+    return ADX_OK;
+}
+
+}  // namespace
+
+extern "C" adx_status adx_autocorr_codes(int device, int n_traj, int n_steps, int n_pos, const uint8_t *codes,
+                                         int max_lag, int64_t *pos_matches, int64_t *traj_matches) {
+    if (n_traj < 1 || n_steps < 1 || n_steps > PICK_MAX_STEPS || n_pos < 1 || !codes || !pos_matches)
+        return fail(ADX_EINVAL, "adx_autocorr_codes: bad argument");
+    adx_status s = autocorr_args_ok("adx_autocorr_codes", n_steps, max_lag, 0);
+    if (s) return s;
+    Problem dev;   // the device checks and a stream
+    dev.device = device;
+    s = dev.init_device();
+    if (s) return s;
+    const size_t L = size_t(max_lag) + 1, R = size_t(n_steps) * size_t(n_traj) * size_t(n_pos);
+    DevBuf<uint8_t> dcodes;
+    DevBuf<uint64_t> planes;
+    DevBuf<unsigned long long> dpos, dtraj;
+    DevBuf<int> bad;
+    const int chunk = traj_autocorr_chunk(n_steps, n_pos, n_traj);
+    MEM_TRY(dcodes.alloc(R));
+    MEM_TRY(planes.alloc(traj_autocorr_plane_words(n_steps, n_pos, chunk)));
+    MEM_TRY(dpos.alloc(size_t(n_pos) * L));
+    MEM_TRY(bad.alloc(1));
+    HIP_TRY(hipMemcpyAsync(dcodes.p, codes, R, hipMemcpyHostToDevice, dev.stream));
+    HIP_TRY(hipMemsetAsync(dpos.p, 0, size_t(n_pos) * L * sizeof(unsigned long long), dev.stream));
+    HIP_TRY(hipMemsetAsync(bad.p, 0, sizeof(int), dev.stream));
+    if (traj_matches) {
+        MEM_TRY(dtraj.alloc(size_t(n_traj) * L));
+        HIP_TRY(hipMemsetAsync(dtraj.p, 0, size_t(n_traj) * L * sizeof(unsigned long long), dev.stream));
+    }
+    for (int w0 = 0; w0 < n_traj; w0 += chunk) {
+        const int nw = std::min(chunk, n_traj - w0);
+        HIP_TRY(launch_autocorr_pack_codes(dcodes.p, n_traj, n_steps, n_pos, w0, nw, planes.p, bad.p, dev.stream));
+        HIP_TRY(launch_autocorr_lags(planes.p, nw, n_pos, n_steps, max_lag, w0, dpos.p, dtraj.p, dev.stream));
+    }
+    int wrong = 0;
+    HIP_TRY(hipMemcpyAsync(&wrong, bad.p, sizeof(int), hipMemcpyDeviceToHost, dev.stream));
+    HIP_TRY(hipMemcpyAsync(pos_matches, dpos.p, size_t(n_pos) * L * sizeof(int64_t), hipMemcpyDeviceToHost, dev.stream));
+    if (traj_matches)
+        HIP_TRY(hipMemcpyAsync(traj_matches, dtraj.p, size_t(n_traj) * L * sizeof(int64_t), hipMemcpyDeviceToHost,
+                               dev.stream));
+    HIP_TRY(hipStreamSynchronize(dev.stream));
+    if (wrong) return fail(ADX_EINVAL, "adx_autocorr_codes: a code outside 1..4");
+    return ADX_OK;
+}
+
+extern "C" adx_status adx_record_autocorr(adx_ctx *c, int max_lag, int discard, int64_t *pos_matches,
+                                          int64_t *walker_matches, int64_t *base_counts, int64_t *outcome_counts,
+                                          unsigned char *changeable, int *n_changeable) {
+    if (!c || !pos_matches) return fail(ADX_EINVAL, "adx_record_autocorr: null argument");
+    auto &rec = c->rec;
+    if (!rec.on) return fail(ADX_ESTATE, "adx_record_autocorr before adx_record_begin");
+    if (rec.broken)
+        return fail(ADX_ESTATE, "adx_record_autocorr: the record is broken (walkers initialised or imported during it, "
+                                "or a failed adx_run_steps); begin a new one");
+    if (rec.rows <= 0) return fail(ADX_ESTATE, "adx_record_autocorr: no step recorded yet");
+    Problem &pb = c->pb;
+    const int W = rec.W, S = rec.rows, N = pb.Nraw;
+    adx_status s = autocorr_args_ok("adx_record_autocorr", S, max_lag, discard);
+    if (s) return s;
+    const int kept = S - discard;
+    const size_t L = size_t(max_lag) + 1;
+    // changeable: in the closure list of a freely mutable position (itself and its partners)
+    std::vector<uint8_t> flag(size_t(N), 0);
+    for (size_t m = 0; m + 1 < c->clo_off.size(); m++)
+        for (int k = c->clo_off[m]; k < c->clo_off[m + 1]; k++) flag[size_t(c->clo_pos[size_t(k)])] = 1;
+    std::vector<int> chg;
+    for (int k = 0; k < N; k++)
+        if (flag[size_t(k)]) chg.push_back(k);
+    const int P = int(chg.size());
+    for (int k = 0; k < N; k++)
+        for (size_t l = 0; l < L; l++) pos_matches[size_t(k) * L + l] = int64_t(W) * int64_t(kept - int(l));
+    if (walker_matches) std::fill(walker_matches, walker_matches + size_t(W) * L, int64_t(0));
+    if (changeable) std::copy(flag.begin(), flag.end(), changeable);
+    if (n_changeable) *n_changeable = P;
+    DevBuf<int> dchg;
+    DevBuf<uint8_t> dflag;
+    DevBuf<uint64_t> planes;
+    DevBuf<unsigned long long> dpos, dwalk, dbase, dout;
+    const int chunk = traj_autocorr_chunk(kept, P, W);
+    HIP_TRY(dchg.upload(chg.data(), chg.size(), pb.stream));
+    HIP_TRY(dflag.upload(flag.data(), flag.size(), pb.stream));
+    MEM_TRY(planes.alloc(traj_autocorr_plane_words(kept, P, chunk)));
+    MEM_TRY(dpos.alloc(size_t(P) * L));
+    MEM_TRY(dwalk.alloc(size_t(W) * L));
+    MEM_TRY(dbase.alloc(size_t(N) * 4));
+    MEM_TRY(dout.alloc(size_t(W) * 4));
+    HIP_TRY(hipMemsetAsync(dpos.p, 0, std::max<size_t>(size_t(P) * L, 1) * sizeof(unsigned long long), pb.stream));
+    HIP_TRY(hipMemsetAsync(dwalk.p, 0, size_t(W) * L * sizeof(unsigned long long), pb.stream));
+    HIP_TRY(hipMemsetAsync(dbase.p, 0, size_t(N) * 4 * sizeof(unsigned long long), pb.stream));
+    AutocorrPackArgs a{};
+    a.seq0 = rec.seq0.p;
+    a.pos = rec.pos.p;
+    a.base = rec.base.p;
+    a.outcome = rec.out.p;
+    a.W = W;
+    a.N = N;
+    a.rows = S;
+    a.discard = discard;
+    a.posmap = rec.posmap.p;
+    a.clo_off = c->d_clo_off.p;
+    a.clo_pos = c->d_clo_pos.p;
+    a.clo_par = c->d_clo_par.p;
+    a.chg = dchg.p;
+    a.changeable = dflag.p;
+    a.P = P;
+    a.nwords = ta_words(kept);
+    a.planes = reinterpret_cast<unsigned long long *>(planes.p);
+    a.base_counts = dbase.p;
+    a.outcome_counts = dout.p;
+    // pack and lag times summed over the chunks: an event before and after each launch
+    const int n_chunks = (W + chunk - 1) / chunk;
+    std::vector<hipEvent_t> ev(size_t(n_chunks) * 3, nullptr);
+    struct Free {
+        std::vector<hipEvent_t> &v;
+        ~Free() {
+            for (auto x : v)
+                if (x) (void)hipEventDestroy(x);
+        }
+    } free_events{ev};
+    for (auto &x : ev) HIP_TRY(hipEventCreate(&x));
+    for (int w0 = 0, i = 0; w0 < W; w0 += chunk, i++) {
+        a.w0 = w0;
+        a.nw = std::min(chunk, W - w0);
+        HIP_TRY(hipEventRecord(ev[size_t(3 * i)], pb.stream));
+        HIP_TRY(launch_autocorr_pack(a, pb.stream));
+        HIP_TRY(hipEventRecord(ev[size_t(3 * i + 1)], pb.stream));
+        HIP_TRY(launch_autocorr_lags(planes.p, a.nw, P, kept, max_lag, w0, dpos.p, dwalk.p, pb.stream));
+        HIP_TRY(hipEventRecord(ev[size_t(3 * i + 2)], pb.stream));
+    }
+    std::vector<int64_t> hpos(std::max<size_t>(size_t(P) * L, 1));
+    HIP_TRY(hipMemcpyAsync(hpos.data(), dpos.p, size_t(P) * L * sizeof(int64_t), hipMemcpyDeviceToHost, pb.stream));
+    if (walker_matches)
+        HIP_TRY(hipMemcpyAsync(walker_matches, dwalk.p, size_t(W) * L * sizeof(int64_t), hipMemcpyDeviceToHost,
+                               pb.stream));
+    if (base_counts)
+        HIP_TRY(hipMemcpyAsync(base_counts, dbase.p, size_t(N) * 4 * sizeof(int64_t), hipMemcpyDeviceToHost, pb.stream));
+    if (outcome_counts)
+        HIP_TRY(hipMemcpyAsync(outcome_counts, dout.p, size_t(W) * 4 * sizeof(int64_t), hipMemcpyDeviceToHost,
+                               pb.stream));
+    HIP_TRY(hipStreamSynchronize(pb.stream));
+    for (int pi = 0; pi < P; pi++)
+        std::copy(hpos.begin() + size_t(pi) * L, hpos.begin() + size_t(pi + 1) * L, pos_matches + size_t(chg[size_t(pi)]) * L);
+    double pack = 0.0, lag = 0.0;
+    for (int i = 0; i < n_chunks; i++) {
+        float x = 0.f, y = 0.f;
+        HIP_TRY(hipEventElapsedTime(&x, ev[size_t(3 * i)], ev[size_t(3 * i + 1)]));
+        HIP_TRY(hipEventElapsedTime(&y, ev[size_t(3 * i + 1)], ev[size_t(3 * i + 2)]));
+        pack += x;
+        lag += y;
+    }
+    c->ac_pack_ms = pack;
+    c->ac_lag_ms = lag;
+    return ADX_OK;
+}
+
+extern "C" adx_status adx_last_autocorr_ms(const adx_ctx *c, double *pack_ms, double *lag_ms) {
+    if (!c || !pack_ms || !lag_ms) return fail(ADX_EINVAL, "adx_last_autocorr_ms: null argument");
+    *pack_ms = c->ac_pack_ms;
+    *lag_ms = c->ac_lag_ms;
+    return ADX_OK;
+}
+
+extern "C" adx_status adx_autocorr_time(const int64_t *matches, int max_lag, int64_t n_series, int64_t kept_steps,
+                                        double baseline, int *tau) {
+    if (!matches || !tau || max_lag < 0 || n_series < 1 || kept_steps < 1 || max_lag > kept_steps - 1)
+        return fail(ADX_EINVAL, "adx_autocorr_time: bad argument (max_lag at most kept_steps - 1 = %lld)",
+                    (long long)(kept_steps - 1));
+    *tau = ta_time(matches, max_lag, n_series, kept_steps, baseline);
     return ADX_OK;
 }

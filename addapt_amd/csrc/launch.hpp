@@ -148,6 +148,42 @@ struct ReplayArgs {
 };
 hipError_t launch_traj_replay(const ReplayArgs &a, hipStream_t stream);
 
+// ---- traj_autocorr.hip: per-position autocorrelation of sequence trajectories (traj_autocorr_core.hpp).
+// The kept steps of every changeable position are packed into two bit planes (low and high
+// bit of code - 1), [walker][position][plane][ta_words(kept)] uint64, for chunks of walkers
+// [w0, w0 + nw) so that the planes stay bounded: traj_autocorr_plane_words(kept, P, chunk).
+// The lag kernel adds each (walker, position, lag)'s matches to pos_matches[P * (max_lag + 1)]
+// (by index into the packed positions) and to walker_matches[W * (max_lag + 1)] (optional);
+// the caller zeroes both and checks 0 <= max_lag <= kept - 1.
+int traj_autocorr_chunk(int kept, int P, int n_traj);
+size_t traj_autocorr_plane_words(int kept, int P, int chunk);
+struct AutocorrPackArgs {
+    const uint8_t *seq0;        // the record, as ReplayArgs
+    const int32_t *pos;
+    const int8_t *base;
+    const int32_t *outcome;
+    int W, N, rows;
+    int discard;                // rows replayed but not kept (< rows)
+    const int *posmap;
+    const int *clo_off, *clo_pos;
+    const uint8_t *clo_par;
+    const int *chg;             // [P] the changeable positions, ascending
+    const uint8_t *changeable;  // [N] 1: in chg
+    int P;
+    int w0, nw;                 // the chunk
+    int nwords;                 // ta_words(rows - discard)
+    unsigned long long *planes;
+    unsigned long long *base_counts;     // [N * 4] A, C, G, U over the kept steps, added to (optional)
+    unsigned long long *outcome_counts;  // [W * 4] outcomes 0..3 over the kept steps, written (optional)
+};
+hipError_t launch_autocorr_pack(const AutocorrPackArgs &a, hipStream_t stream);
+// codes[(r * W + w) * P + p], S steps; *bad is set to 1 at a code outside 1..4
+hipError_t launch_autocorr_pack_codes(const uint8_t *codes, int W, int S, int P, int w0, int nw, uint64_t *planes,
+                                      int *bad, hipStream_t stream);
+hipError_t launch_autocorr_lags(const uint64_t *planes, int nw, int P, int kept, int max_lag, int w0,
+                                unsigned long long *pos_matches, unsigned long long *walker_matches,
+                                hipStream_t stream);
+
 // ---- mc_step.hip
 hipError_t launch_steps(const KArgs &ka, const StepArgs &st, hipStream_t stream, hipEvent_t *evs);
 hipError_t launch_rescore(const KArgs &ka, const StepArgs &st, double *tv, hipStream_t stream);

@@ -3,7 +3,8 @@
 //
 //   addapt <config>... [-n <num>] [-T <schedule>] [-r <seed>] [-o <path>]
 //                      [-i <steps>] [--walkers <W>] [--gpu <id>] [--params <file>]
-//                      [--reference-loop] [--picks <path>] [--pick-window <steps>]
+//                      [--reference-loop] [--picks <path>] [--pick-window <steps>|auto]
+//                      [--autocorr <path>] [--autocorr-lag <steps>] [--autocorr-discard <steps>]
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -44,8 +45,21 @@ static const char USAGE[] =
     "    With --walkers: record every walker's trajectory on the GPU and write the\n"
     "    peaks of each (scores at or above the trajectory's 75th percentile, best\n"
     "    first, at least the pick window apart) with the sequences there.\n"
-    "  --pick-window <steps>                  [default: 500]\n"
-    "    The least distance between two picks of one trajectory.\n"
+    "  --pick-window <steps>|auto             [default: 500]\n"
+    "    The least distance between two picks of one trajectory.  auto: the\n"
+    "    correlation time of the sequence autocorrelation (see --autocorr; computed\n"
+    "    with its defaults if --autocorr is absent), or 500 with a warning if the\n"
+    "    autocorrelation has not decayed.\n"
+    "  --autocorr <path>\n"
+    "    With --walkers: record every walker's trajectory on the GPU and write the\n"
+    "    per-position autocorrelation of the sequences: '#' lines with the\n"
+    "    correlation time, the baseline and the shares of the four outcomes, then\n"
+    "    one row per lag: the lag, the autocorrelation pooled over all walkers and\n"
+    "    changeable positions, and one column per changeable position (0-based).\n"
+    "  --autocorr-lag <steps>                 [default: 500]\n"
+    "    The largest lag (clipped to the kept steps - 1).\n"
+    "  --autocorr-discard <steps>             [default: 100]\n"
+    "    Steps dropped from the start of every trajectory (equilibration).\n"
     "  --gpu <id>                             [default: 0]\n"
     "  --params <file>  Energy parameters (ViennaRNA 2.0 format).\n"
     "  --reference-loop  Run the reference's single-walker loop (one GPU fold call\n"
@@ -87,10 +101,32 @@ static void write_picks(const std::string &path, const BatchResult &res, const s
     std::fclose(f);
 }
 
+// The sequence autocorrelation of a batched run (what the reference's auto_corr
+// plots and mc_stats prints): '#' lines, then one row per lag.
+static void write_autocorr(const std::string &path, const Autocorr &ac) {
+    FILE *f = std::fopen(path.c_str(), "w");
+    if (!f) throw std::string("couldn't open '" + path + "' for writing");
+    std::fprintf(f, "# tau: %d\n# baseline: %.6f\n# kept steps: %lld (discarded %d)\n", ac.tau, ac.baseline,
+                 (long long)ac.kept_steps, ac.discard);
+    static const char *names[4] = {"reject", "accept_worsened", "accept_unchanged", "accept_improved"};
+    for (int k = 0; k < 4; k++) std::fprintf(f, "# %s: %.2f%%\n", names[k], 100.0 * ac.outcome_share[k]);
+    std::fprintf(f, "lag\tpooled");
+    for (int p : ac.positions) std::fprintf(f, "\t%d", p);
+    std::fprintf(f, "\n");
+    const size_t L = size_t(ac.max_lag) + 1;
+    for (size_t k = 0; k < L; k++) {
+        std::fprintf(f, "%zu\t%.6f", k, ac.pooled[k]);
+        for (size_t i = 0; i < ac.positions.size(); i++) std::fprintf(f, "\t%.6f", ac.curves[i * L + k]);
+        std::fprintf(f, "\n");
+    }
+    std::fclose(f);
+}
+
 int main(int argc, char **argv) {
     std::vector<std::string> configs;
-    std::string temp, out = "traj.tsv", params, picks;
-    int num = 100, interval = 1, walkers = 1, gpu = 0, pick_window = 500;
+    std::string temp, out = "traj.tsv", params, picks, autocorr;
+    int num = 100, interval = 1, walkers = 1, gpu = 0, pick_window = 500, autocorr_lag = 500, autocorr_discard = 100;
+    bool auto_window = false;
     unsigned long seed = 0;
     bool ref_loop = false;
     try {
@@ -109,7 +145,14 @@ int main(int argc, char **argv) {
             else if (a == "-i" || a == "--output-interval") interval = std::stoi(val("--output-interval"));
             else if (a == "--walkers") walkers = std::stoi(val("--walkers"));
             else if (a == "--picks") picks = val("--picks");
-            else if (a == "--pick-window") pick_window = std::stoi(val("--pick-window"));
+            else if (a == "--pick-window") {
+                const std::string v = val("--pick-window");
+                auto_window = v == "auto";
+                if (!auto_window) pick_window = std::stoi(v);
+            }
+            else if (a == "--autocorr") autocorr = val("--autocorr");
+            else if (a == "--autocorr-lag") autocorr_lag = std::stoi(val("--autocorr-lag"));
+            else if (a == "--autocorr-discard") autocorr_discard = std::stoi(val("--autocorr-discard"));
             else if (a == "--gpu") gpu = std::stoi(val("--gpu"));
             else if (a == "--params") params = val("--params");
             else if (a == "--reference-loop") ref_loop = true;
@@ -121,7 +164,11 @@ int main(int argc, char **argv) {
             return 1;
         }
         if (!picks.empty() && walkers <= 1) throw std::string("--picks needs --walkers <W> with W > 1");
-        if (!picks.empty() && pick_window < 1) throw std::string("--pick-window must be at least 1");
+        if (!picks.empty() && !auto_window && pick_window < 1) throw std::string("--pick-window must be at least 1");
+        if (!autocorr.empty() && walkers <= 1) throw std::string("--autocorr needs --walkers <W> with W > 1");
+        const bool correlating = !autocorr.empty() || (!picks.empty() && auto_window);
+        if (correlating && autocorr_lag < 1) throw std::string("--autocorr-lag must be at least 1");
+        if (correlating && autocorr_discard < 0) throw std::string("--autocorr-discard must not be negative");
         if (!params.empty()) set_parameter_file(params);
         DevicePtr device = device_from_yaml(configs);
         ScoreFunctionPtr sf = scorefxn_from_yaml(configs);
@@ -134,7 +181,12 @@ int main(int argc, char **argv) {
         if (walkers > 1) {
             std::vector<uint32_t> seeds(walkers);
             for (int w = 0; w < walkers; w++) seeds[w] = uint32_t(seed + w);
-            auto res = mc->apply_batch(device, seeds, gpu, picks.empty() ? 0 : pick_window);
+            BatchOptions opt;
+            opt.pick_window = picks.empty() || auto_window ? 0 : pick_window;
+            opt.auto_window = !picks.empty() && auto_window;
+            opt.autocorr_lag = correlating ? autocorr_lag : 0;
+            opt.autocorr_discard = correlating ? autocorr_discard : 0;
+            auto res = mc->apply_batch(device, seeds, gpu, opt);
             FILE *f = std::fopen(out.c_str(), "w");
             if (!f) throw std::string("couldn't open '" + out + "' for writing");
             std::fprintf(f, "walker\tseed\tscore\treject\taccept_worsened\taccept_unchanged\taccept_improved\tseq\n");
@@ -147,6 +199,7 @@ int main(int argc, char **argv) {
             }
             std::fclose(f);
             if (!picks.empty()) write_picks(picks, res, seeds);
+            if (!autocorr.empty()) write_autocorr(autocorr, res.autocorr);
             return 0;
         }
         *mc += std::make_shared<ProgressReporter>();

@@ -252,8 +252,21 @@ void build_setup(const MonteCarlo &mc, DeviceConstPtr device, int g, EngineSetup
 }  // namespace
 
 BatchResult MonteCarlo::apply_batch(DevicePtr device, const std::vector<uint32_t> &seeds, int g, int pick_window) const {
+    BatchOptions opt;
+    opt.pick_window = pick_window;
+    return apply_batch(device, seeds, g, opt);
+}
+
+BatchResult MonteCarlo::apply_batch(DevicePtr device, const std::vector<uint32_t> &seeds, int g,
+                                    const BatchOptions &opt) const {
     if (!gpu_expressible()) throw string("apply_batch: the score function / moves / thermostat are not GPU-expressible");
-    if (pick_window < 0) throw string("apply_batch: negative pick window");
+    if (opt.pick_window < 0) throw string("apply_batch: negative pick window");
+    if (opt.autocorr_lag < 0 || opt.autocorr_discard < 0) throw string("apply_batch: negative autocorrelation lag or discard");
+    if (opt.auto_window && opt.autocorr_lag <= 0)
+        throw string("apply_batch: an automatic pick window needs the autocorrelation (autocorr_lag > 0)");
+    if (opt.autocorr_lag > 0 && steps_ > 0 && opt.autocorr_discard >= steps_)   // before the run, not after it
+        throw string("apply_batch: autocorrelation discard " + std::to_string(opt.autocorr_discard) +
+                     " leaves none of the " + std::to_string(steps_) + " steps");
     EngineSetup e;
     build_setup(*this, device, g, e);
     adx_ctx *raw = nullptr;
@@ -261,8 +274,9 @@ BatchResult MonteCarlo::apply_batch(DevicePtr device, const std::vector<uint32_t
     gpu::CtxPtr ctx(raw);
     const int W = int(seeds.size());
     gpu::check(adx_walkers_init(ctx.get(), W, nullptr, seeds.data()));
-    const bool picking = pick_window > 0 && steps_ > 0;
-    if (picking) gpu::check(adx_record_begin(ctx.get(), steps_));
+    const bool correlating = opt.autocorr_lag > 0 && steps_ > 0;
+    const bool picking = (opt.pick_window > 0 || opt.auto_window) && steps_ > 0;
+    if (picking || correlating) gpu::check(adx_record_begin(ctx.get(), steps_));
     if (steps_ > 0) gpu::check(adx_run_steps(ctx.get(), steps_, nullptr));
     const size_t N = e.seq.size();
     std::vector<char> seqs(N * W);
@@ -271,6 +285,56 @@ BatchResult MonteCarlo::apply_batch(DevicePtr device, const std::vector<uint32_t
     gpu::check(adx_walkers_download(ctx.get(), seqs.data(), scores.data(), cnt.data()));
     BatchResult out;
     out.resize(W);
+    if (correlating) {
+        Autocorr &ac = out.autocorr;
+        ac.discard = opt.autocorr_discard;
+        ac.kept_steps = steps_ - ac.discard;
+        ac.max_lag = int(std::min<int64_t>(opt.autocorr_lag, ac.kept_steps - 1));
+        const size_t L = size_t(ac.max_lag) + 1;
+        std::vector<int64_t> pm(N * L), bc(4 * N), oc(4 * size_t(W));
+        std::vector<unsigned char> flag(N);
+        int nch = 0;
+        gpu::check(adx_record_autocorr(ctx.get(), ac.max_lag, ac.discard, pm.data(), nullptr, bc.data(), oc.data(),
+                                       flag.data(), &nch));
+        std::vector<int64_t> pooled(L, 0);
+        double base = 0.0;
+        for (size_t p = 0; p < N; p++) {
+            if (!flag[p]) continue;
+            ac.positions.push_back(int(p));
+            double sq = 0.0;
+            for (int c4 = 0; c4 < 4; c4++) {
+                const double f = double(bc[4 * p + c4]) / double(int64_t(W) * ac.kept_steps);
+                sq += f * f;
+            }
+            base += sq;
+            for (size_t k = 0; k < L; k++) {
+                pooled[k] += pm[p * L + k];
+                ac.curves.push_back(double(pm[p * L + k]) / (double(W) * double(ac.kept_steps - int64_t(k))));
+            }
+        }
+        ac.pooled.assign(L, 1.0);
+        if (nch > 0) {
+            ac.baseline = base / double(nch);
+            for (size_t k = 0; k < L; k++)
+                ac.pooled[k] = double(pooled[k]) / (double(int64_t(W) * nch) * double(ac.kept_steps - int64_t(k)));
+            gpu::check(adx_autocorr_time(pooled.data(), ac.max_lag, int64_t(W) * nch, ac.kept_steps, ac.baseline, &ac.tau));
+        }
+        for (int c4 = 0; c4 < 4; c4++) {
+            int64_t n = 0;
+            for (int w = 0; w < W; w++) n += oc[size_t(w) * 4 + c4];
+            ac.outcome_share[c4] = double(n) / double(int64_t(W) * ac.kept_steps);
+        }
+    }
+    int pick_window = opt.pick_window;
+    if (picking && opt.auto_window) {
+        pick_window = out.autocorr.tau;
+        if (pick_window < 1) {
+            pick_window = 500;
+            std::cerr << "Warning: the correlation time is " << out.autocorr.tau
+                      << (out.autocorr.tau < 0 ? " (the autocorrelation has not decayed within " : " (nothing changed within ")
+                      << out.autocorr.max_lag << " lags); picking with a window of 500 steps instead" << std::endl;
+        }
+    }
     if (picking) {
         const size_t cap = size_t((steps_ - 1) / pick_window + 1);
         std::vector<int> n(W);
@@ -280,13 +344,13 @@ BatchResult MonteCarlo::apply_batch(DevicePtr device, const std::vector<uint32_t
         out.base_counts.assign(4 * N, 0);
         gpu::check(adx_record_picks(ctx.get(), pick_window, int(cap), n.data(), psteps.data(), pscores.data(),
                                     pseqs.data(), out.base_counts.data()));
-        gpu::check(adx_record_end(ctx.get()));
         for (int w = 0; w < W; w++)
             for (int k = 0; k < n[w]; k++) {   // n[w] = -1 (a non-finite score): no picks
                 const size_t o = size_t(w) * cap + k;
                 out[w].picks.push_back(Pick{w, psteps[o], pscores[o], string(&pseqs[o * N], N)});
             }
     }
+    if (picking || correlating) gpu::check(adx_record_end(ctx.get()));
     for (int w = 0; w < W; w++) {
         out[w].device = device->copy();
         for (size_t k = 0; k < N; k++) out[w].device->mutate(int(k), seqs[size_t(w) * N + k]);

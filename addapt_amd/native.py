@@ -88,6 +88,7 @@ EXPORTS = [
     "adx_fold_ensemble_structures", "adx_ensemble_structures_batch", "adx_walkers_ensemble_structures",
     "adx_last_ensemble_ms",
     "adx_pick_scores", "adx_record_begin", "adx_record_end", "adx_record_picks", "adx_last_pick_ms",
+    "adx_autocorr_codes", "adx_record_autocorr", "adx_last_autocorr_ms", "adx_autocorr_time",
 ]
 
 _lib = None
@@ -167,6 +168,14 @@ def lib():
         L.adx_record_picks.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int64),
                                        C.POINTER(C.c_double), C.c_char_p, C.POINTER(C.c_int64)]
         L.adx_last_pick_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.adx_autocorr_codes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint8), C.c_int,
+                                         C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.adx_record_autocorr.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                          C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_ubyte),
+                                          C.POINTER(C.c_int)]
+        L.adx_last_autocorr_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.adx_autocorr_time.argtypes = [C.POINTER(C.c_int64), C.c_int, C.c_int64, C.c_int64, C.c_double,
+                                        C.POINTER(C.c_int)]
         _lib = L
     return _lib
 
@@ -207,6 +216,36 @@ def pick_scores(scores, window, cap=None, device=0):
                                  n.ctypes.data_as(C.POINTER(C.c_int)), st.ctypes.data_as(C.POINTER(C.c_int32))))
     st = st[:W * cap].reshape(W, cap)
     return [None if n[w] < 0 else [int(x) for x in st[w, :n[w]]] for w in range(W)]
+
+
+def autocorr_codes(codes, max_lag, device=0):
+    """(pos_matches, traj_matches) of trajectories given as a (steps, trajectories,
+    positions) uint8 array of base codes 1..4 (adx_autocorr_codes): for each lag
+    k in 0..max_lag the number of steps i < steps - k with codes[i + k] == codes[i],
+    as int64 arrays (positions, max_lag + 1) summed over the trajectories and
+    (trajectories, max_lag + 1) summed over the positions.  Dividing by
+    trajectories * (steps - k), or positions * (steps - k), gives the autocorrelation."""
+    cd = np.ascontiguousarray(codes, np.uint8)
+    if cd.ndim != 3:
+        raise ValueError("autocorr_codes: codes must be (steps, trajectories, positions)")
+    S, W, P = cd.shape
+    pm = np.zeros((max(P, 1), max(max_lag, 0) + 1), np.int64)
+    tm = np.zeros((max(W, 1), max(max_lag, 0) + 1), np.int64)
+    _check(lib().adx_autocorr_codes(device, W, S, P, cd.ctypes.data_as(C.POINTER(C.c_uint8)), max_lag,
+                                    pm.ctypes.data_as(C.POINTER(C.c_int64)), tm.ctypes.data_as(C.POINTER(C.c_int64))))
+    return pm, tm
+
+
+def autocorr_time(matches, n_series, kept_steps, baseline):
+    """The correlation time of a pooled curve of match counts for the lags
+    0..len(matches) - 1 (adx_autocorr_time; host arithmetic): the least lag
+    k >= 1 at which matches[k] / (n_series * (kept_steps - k)) - baseline has
+    fallen to (1 - baseline) / e; -1 if none has, 0 if baseline >= 1."""
+    m = np.ascontiguousarray(matches, np.int64)
+    tau = C.c_int()
+    _check(lib().adx_autocorr_time(m.ctypes.data_as(C.POINTER(C.c_int64)), len(m) - 1, n_series, kept_steps,
+                                   baseline, C.byref(tau)))
+    return tau.value
 
 
 class Params:
@@ -553,6 +592,43 @@ class Engine:
             out.append([(int(st[w * cap + k]), float(sc[w * cap + k]),
                          raw[(w * cap + k) * N:(w * cap + k + 1) * N].decode()) for k in range(n[w])])
         return out, cnt
+
+    def autocorr(self, max_lag, discard=0):
+        """The per-position autocorrelation of the steps recorded so far, the first
+        `discard` dropped (adx_record_autocorr).  A dict: pos_matches (N, max_lag + 1)
+        and walker_matches (W, max_lag + 1), int64 match counts summed over the
+        walkers and over the changeable positions; base_counts (N, 4) and
+        outcome_counts (W, 4) over the kept steps; changeable (N,) bool; kept_steps;
+        baseline, the chance that two independent draws at a changeable position
+        match; pooled, the autocorrelation over all walkers and changeable positions
+        per lag; tau, its correlation time (adx_autocorr_time), in steps."""
+        W, N, L = self.W, self.N, max(max_lag, 0) + 1
+        pm, wm = np.zeros((N, L), np.int64), np.zeros((max(W, 1), L), np.int64)
+        bc, oc = np.zeros((N, 4), np.int64), np.zeros((max(W, 1), 4), np.int64)
+        ch = np.zeros(N, np.uint8)
+        nch = C.c_int()
+        i64 = C.POINTER(C.c_int64)
+        _check(lib().adx_record_autocorr(self.ptr, max_lag, discard, pm.ctypes.data_as(i64), wm.ctypes.data_as(i64),
+                                         bc.ctypes.data_as(i64), oc.ctypes.data_as(i64),
+                                         ch.ctypes.data_as(C.POINTER(C.c_ubyte)), C.byref(nch)))
+        kept = (self._rec_rows or 0) - discard
+        ch = ch.astype(bool)
+        pooled_m = pm[ch].sum(axis=0)
+        if nch.value > 0:
+            f = bc[ch] / float(W * kept)
+            baseline = float((f * f).sum(axis=1).mean())
+            tau = autocorr_time(pooled_m, W * nch.value, kept, baseline)
+            pooled = pooled_m / (float(W * nch.value) * (kept - np.arange(L)))
+        else:   # nothing can change
+            baseline, tau, pooled = 1.0, 0, np.ones(L)
+        return dict(pos_matches=pm, walker_matches=wm[:W], base_counts=bc, outcome_counts=oc[:W], changeable=ch,
+                    kept_steps=kept, baseline=baseline, pooled=pooled, tau=tau)
+
+    def last_autocorr_ms(self):
+        """(plane packing ms, lag kernel ms) of the last autocorr() call, from HIP events."""
+        a, b = C.c_double(), C.c_double()
+        _check(lib().adx_last_autocorr_ms(self.ptr, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def last_pick_ms(self):
         """(picking kernels ms, replay kernel ms) of the last picks() call, from HIP events."""

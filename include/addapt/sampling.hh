@@ -162,10 +162,36 @@ struct WalkerResult {
     std::vector<Pick> picks;   ///< ascending steps; empty without a pick window
 };
 
+/// the per-position autocorrelation of the walkers' sequence trajectories (what
+/// the reference's auto_corr script plots from a trajectory file), over the
+/// steps kept after `discard`: at lag k the share of steps i whose base equals
+/// that of step i + k
+struct Autocorr {
+    int max_lag = -1;                  ///< -1: not computed
+    int discard = 0;
+    int64_t kept_steps = 0;
+    std::vector<int> positions;        ///< the changeable positions (0-based): freely mutable ones and their partners
+    std::vector<double> curves;        ///< curves[i * (max_lag + 1) + k]: position positions[i], all walkers
+    std::vector<double> pooled;        ///< [max_lag + 1] over all walkers and changeable positions
+    double baseline = 1.0;             ///< the chance that two independent draws at a changeable position match
+    int tau = 0;                       ///< the correlation time of `pooled` in steps (adx_autocorr_time); -1: not decayed
+    double outcome_share[4] = {0, 0, 0, 0};   ///< reject, accept worsened / unchanged / improved over the kept steps
+};
+
 /// the walkers' results; with a pick window also how often A, C, G, U stand at
 /// each position over all walkers' picks (base_counts[4 * position + base])
 struct BatchResult : std::vector<WalkerResult> {
     std::vector<int64_t> base_counts;
+    Autocorr autocorr;                 ///< filled with BatchOptions::autocorr_lag > 0
+};
+
+/// what a batched run does besides stepping
+struct BatchOptions {
+    int pick_window = 0;        ///< > 0: pick each trajectory's peaks at least this many steps apart
+    bool auto_window = false;   ///< pick with the correlation time as window (needs autocorr_lag > 0);
+                                ///< if it is below 1 (not decayed, or nothing changed) with 500, warning on stderr
+    int autocorr_lag = 0;       ///< > 0: the autocorrelation up to this lag (clipped to the kept steps - 1)
+    int autocorr_discard = 0;   ///< steps dropped from the start (equilibration); must be below the number of steps
 };
 
 class MonteCarlo {
@@ -182,6 +208,10 @@ public:
     /// steps apart) come back as WalkerResult::picks
     BatchResult apply_batch(DevicePtr device, const std::vector<uint32_t> &seeds, int gpu = 0,
                             int pick_window = 0) const;
+    /// the same with options: picks, the sequence autocorrelation of the recorded
+    /// trajectories (BatchResult::autocorr), and picks whose window is its correlation time
+    BatchResult apply_batch(DevicePtr device, const std::vector<uint32_t> &seeds, int gpu,
+                            const BatchOptions &options) const;
     /// true if the fused GPU engine can run this setup
     bool gpu_expressible() const;
 

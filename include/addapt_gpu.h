@@ -412,6 +412,55 @@ adx_status adx_record_picks(adx_ctx *ctx, int window, int cap, int *n_picks, int
  * picking kernels and the replay kernel. */
 adx_status adx_last_pick_ms(const adx_ctx *ctx, double *pick_ms, double *replay_ms);
 
+/* ------------------------------------------------------------------------
+ * The per-position autocorrelation of sequence trajectories on the device
+ * (what the reference's auto_corr tool computes from a trajectory file): the
+ * measure of the pick window.  For one series x[0..S) of bases and a lag k,
+ *   m(k) = #{ i in [0, S - k) : x[i + k] == x[i] },
+ * the autocorrelation being m(k) / (S - k).  The calls return the integer
+ * counts, summed over trajectories or over positions; the caller divides.
+ * A lag may be at most S - 1 (else ADX_EINVAL naming that lag).
+ * ---------------------------------------------------------------------- */
+
+/* Stateless: codes = n_steps * n_traj * n_pos bytes, step-major
+ * (codes[(r * n_traj + w) * n_pos + p], values 1..4, else ADX_EINVAL).
+ * pos_matches = n_pos * (max_lag + 1) int64 summed over trajectories;
+ * traj_matches = n_traj * (max_lag + 1) int64 summed over positions (optional). */
+adx_status adx_autocorr_codes(int device, int n_traj, int n_steps, int n_pos, const uint8_t *codes,
+                              int max_lag, int64_t *pos_matches, int64_t *traj_matches);
+
+/* The same over the steps recorded so far (adx_record_begin), the first
+ * `discard` dropped: x[i] is the base after recorded row discard + i, the
+ * sequence adx_record_picks returns for that step, S' = rows - discard.
+ * A position is changeable if it is in the closure list of a freely mutable
+ * position (the position itself and the partners that get its complement);
+ * every other position matches at every step.
+ * pos_matches = N * (max_lag + 1), summed over walkers; optional (NULL):
+ * walker_matches = W * (max_lag + 1) summed over the changeable positions,
+ * base_counts = N * 4 (A, C, G, U over the kept steps of all walkers),
+ * outcome_counts = W * 4 (kept steps; order of adx_trace.outcome),
+ * changeable = N flags, *n_changeable.
+ * max_lag < 0, discard < 0, discard >= rows or max_lag > S' - 1: ADX_EINVAL;
+ * before adx_record_begin, with nothing recorded or on a broken record:
+ * ADX_ESTATE, as adx_record_picks.  May be repeated and interleaved with
+ * adx_record_picks; touches neither the walkers nor the record. */
+adx_status adx_record_autocorr(adx_ctx *ctx, int max_lag, int discard, int64_t *pos_matches,
+                               int64_t *walker_matches, int64_t *base_counts, int64_t *outcome_counts,
+                               unsigned char *changeable, int *n_changeable);
+/* Device time (ms, HIP events) of the context's last adx_record_autocorr:
+ * packing the bit planes (with the replay) and the lag kernel. */
+adx_status adx_last_autocorr_ms(const adx_ctx *ctx, double *pack_ms, double *lag_ms);
+
+/* Host arithmetic only, no GPU: the correlation time of a pooled curve.
+ * a_k = matches[k] / (n_series * (kept_steps - k)); *tau = the least k >= 1
+ * with a_k - baseline <= (1 - baseline) / e; -1 if no lag up to max_lag does
+ * (the curve has not decayed: ask for more lags); 0 if baseline >= 1 (nothing
+ * ever changed).  For a record the baseline is the chance that two
+ * independent draws match: the mean over the changeable positions of
+ * sum_c f_pc^2, f_pc = base_counts[p][c] / (W * S'). */
+adx_status adx_autocorr_time(const int64_t *matches, int max_lag, int64_t n_series, int64_t kept_steps,
+                             double baseline, int *tau);
+
 /* Variant v of the score: which (context, condition, macrostate or -1). */
 adx_status adx_variant_desc(const adx_ctx *ctx, int v, int *context, int *condition,
                             int *macrostate);
