@@ -305,3 +305,19 @@ def test_overrides_at_interior_pairs(native, oracle, monkeypatch, N, cond, env, 
     pairs = pair_probe.pair_sets(seq, _matrix(oracle, seq, cond), K_SETS, PER_SET)[0]
     terms = _pair_terms(pairs, cond) + [("apo", 0, True, 1.0), ("holo", 0, True, 1.0)]
     _probe(native, oracle, "override-%d-%s" % (N, cond), seq, terms, expect)
+
+
+# the lengths around which the longest diagonal (span 4, N - 4 cells) takes one more lane-set:
+# 64 -> 65 cells in outside_cells_kernel (one -> two), 128 -> 129 in outside_ring_kernel (two -> three)
+LANE_SET_BOUNDARIES = [(N, cond) for N in (68, 69, 132, 133) for cond in ("apo", "holo")]
+
+
+@pytest.mark.parametrize("N,cond", LANE_SET_BOUNDARIES, ids=["%d-%s" % c for c in LANE_SET_BOUNDARIES])
+def test_lane_set_boundaries(native, oracle, N, cond):
+    """The lane-set count of the records, the finalize and the exterior adjoint, and
+    the form of the finalize's sums over the multiloop parts, change with the
+    diagonal's cell count at exactly these lengths."""
+    seq = pair_probe.synthetic_anchor(N)
+    pairs = pair_probe.pair_sets(seq, _matrix(oracle, seq, cond), K_SETS, PER_SET)[0]
+    terms = _pair_terms(pairs, cond) + [("apo", 0, True, 1.0), ("holo", 0, True, 1.0)]
+    _probe(native, oracle, "lanesets-%d-%s" % (N, cond), seq, terms, _default_names(N))
