@@ -1212,6 +1212,7 @@ struct adx_ctx {
     } rec;
     double pick_ms = 0.0, replay_ms = 0.0;   // the last adx_record_picks, from HIP events
     double ac_pack_ms = 0.0, ac_lag_ms = 0.0;   // the last adx_record_autocorr, from HIP events
+    double design_select_ms = 0.0, design_hist_ms = 0.0;   // the last adx_record_designs, from HIP events
 
     ~adx_ctx() {
         if (ev0) (void)hipEventDestroy(ev0);
@@ -2154,6 +2155,25 @@ extern "C" adx_status adx_record_end(adx_ctx *c) {
     return ADX_OK;
 }
 
+// what the replay reads of the context's record; the picks and the outputs are the caller's
+static ReplayArgs record_replay_args(const adx_ctx *c) {
+    const auto &rec = c->rec;
+    ReplayArgs a{};
+    a.seq0 = rec.seq0.p;
+    a.pos = rec.pos.p;
+    a.base = rec.base.p;
+    a.outcome = rec.out.p;
+    a.W = rec.W;
+    a.N = c->pb.Nraw;
+    a.rows = rec.rows;
+    a.posmap = rec.posmap.p;
+    a.clo_off = c->d_clo_off.p;
+    a.clo_pos = c->d_clo_pos.p;
+    a.clo_par = c->d_clo_par.p;
+    a.lower = rec.lower.p;
+    return a;
+}
+
 extern "C" adx_status adx_record_picks(adx_ctx *c, int window, int cap, int *n_picks, int64_t *steps, double *scores,
                                        char *seqs, int64_t *base_counts) {
     if (!c || !n_picks || !steps) return fail(ADX_EINVAL, "adx_record_picks: null argument");
@@ -2194,19 +2214,7 @@ extern "C" adx_status adx_record_picks(adx_ctx *c, int window, int cap, int *n_p
     if (s) return s;
     HIP_TRY(hipEventRecord(ev.e[1], pb.stream));
     if (seqs || base_counts) {
-        ReplayArgs a{};
-        a.seq0 = rec.seq0.p;
-        a.pos = rec.pos.p;
-        a.base = rec.base.p;
-        a.outcome = rec.out.p;
-        a.W = W;
-        a.N = N;
-        a.rows = S;
-        a.posmap = rec.posmap.p;
-        a.clo_off = c->d_clo_off.p;
-        a.clo_pos = c->d_clo_pos.p;
-        a.clo_par = c->d_clo_par.p;
-        a.lower = rec.lower.p;
+        ReplayArgs a = record_replay_args(c);
         a.n_picks = dn.p;
         a.steps = dst.p;
         a.cap = cap;
@@ -2421,5 +2429,221 @@ extern "C" adx_status adx_autocorr_time(const int64_t *matches, int max_lag, int
         return fail(ADX_EINVAL, "adx_autocorr_time: bad argument (max_lag at most kept_steps - 1 = %lld)",
                     (long long)(kept_steps - 1));
     *tau = ta_time(matches, max_lag, n_series, kept_steps, baseline);
+    return ADX_OK;
+}
+
+// ================================================================== designs
+// (design_select.hip; the rule: design_select_core.hpp)
+namespace {
+
+// the device side of one selection over M entries: the buffers and their initial values
+struct DesignWork {
+    DevBuf<uint64_t> planes, rplanes, keys, keys_tmp, lead;
+    DevBuf<int32_t> idx, idx_tmp, member_rank, leader_rank, member_of, sizes, leaders;
+    DevBuf<int> hist, ctl;   // ctl: the kernels' flags [2] and state [3]
+    DevBuf<unsigned long long> pair;
+    DesignArgs a{};
+
+    adx_status alloc(int M, int N, int radius, int K, bool with_hist, hipStream_t s) {
+        const size_t m = size_t(M), pw = 2 * size_t((N + 63) / 64);
+        MEM_TRY(planes.alloc(pw * m));
+        MEM_TRY(rplanes.alloc(pw * m));
+        MEM_TRY(keys.alloc(m));
+        MEM_TRY(keys_tmp.alloc(m));
+        MEM_TRY(idx.alloc(m));
+        MEM_TRY(idx_tmp.alloc(m));
+        MEM_TRY(hist.alloc(256 * size_t(design_sort_blocks(M))));
+        MEM_TRY(ctl.alloc(5));
+        MEM_TRY(member_rank.alloc(m));
+        MEM_TRY(member_of.alloc(m));
+        MEM_TRY(leader_rank.alloc(size_t(K)));
+        MEM_TRY(lead.alloc(pw * size_t(K)));
+        MEM_TRY(sizes.alloc(size_t(K)));
+        MEM_TRY(leaders.alloc(size_t(K)));
+        HIP_TRY(hipMemsetAsync(ctl.p, 0, 5 * sizeof(int), s));
+        HIP_TRY(hipMemsetAsync(member_rank.p, 0xff, m * sizeof(int32_t), s));
+        HIP_TRY(hipMemsetAsync(sizes.p, 0, size_t(K) * sizeof(int32_t), s));
+        if (with_hist) {
+            MEM_TRY(pair.alloc(size_t(N) + 1));
+            HIP_TRY(hipMemsetAsync(pair.p, 0, (size_t(N) + 1) * sizeof(unsigned long long), s));
+        }
+        a.M = M;
+        a.N = N;
+        a.radius = radius;
+        a.K = K;
+        a.planes = planes.p;
+        a.order = idx.p;
+        a.rank_planes = rplanes.p;
+        a.flags = ctl.p;
+        a.state = ctl.p + 2;
+        a.member_rank = member_rank.p;
+        a.leader_rank = leader_rank.p;
+        a.lead_planes = lead.p;
+        a.member_of = member_of.p;
+        a.sizes = sizes.p;
+        a.leaders = leaders.p;
+        return ADX_OK;
+    }
+};
+
+adx_status design_args_ok(const char *who, int length, int radius, int max_designs) {
+    if (length < 1 || length > 255)
+        return fail(ADX_EINVAL, "%s: sequence length %d outside [1, 255]", who, length);
+    if (radius < 0) return fail(ADX_EINVAL, "%s: radius %d < 0", who, radius);
+    if (max_designs < 1) return fail(ADX_EINVAL, "%s: max_designs %d < 1", who, max_designs);
+    return ADX_OK;
+}
+
+}  // namespace
+
+extern "C" adx_status adx_select_designs(int device, int n_seqs, int length, const char *seqs, const double *scores,
+                                         int radius, int max_designs, int *n_designs, int32_t *leaders, int32_t *sizes,
+                                         int32_t *member_of, int64_t *pair_hist) {
+    if (n_seqs < 1 || !seqs || !scores || !n_designs || !leaders || !sizes)
+        return fail(ADX_EINVAL, "adx_select_designs: bad argument");
+    adx_status s = design_args_ok("adx_select_designs", length, radius, max_designs);
+    if (s) return s;
+    Problem dev;   // the device checks and a stream
+    dev.device = device;
+    s = dev.init_device();
+    if (s) return s;
+    const int M = n_seqs, N = length, K = std::min(max_designs, M);
+    DevBuf<char> dseq;
+    DevBuf<double> dsc;
+    DesignWork w;
+    MEM_TRY(dseq.alloc(size_t(M) * N));
+    MEM_TRY(dsc.alloc(size_t(M)));
+    HIP_TRY(hipMemcpyAsync(dseq.p, seqs, size_t(M) * N, hipMemcpyHostToDevice, dev.stream));
+    HIP_TRY(hipMemcpyAsync(dsc.p, scores, size_t(M) * sizeof(double), hipMemcpyHostToDevice, dev.stream));
+    s = w.alloc(M, N, radius, K, pair_hist != nullptr, dev.stream);
+    if (s) return s;
+    HIP_TRY(launch_design_pack(dseq.p, dsc.p, N, M, nullptr, nullptr, 0, M, w.planes.p, w.keys.p, w.idx.p, nullptr,
+                               w.a.flags, dev.stream));
+    HIP_TRY(launch_design_order(w.keys.p, w.idx.p, w.keys_tmp.p, w.idx_tmp.p, M, w.hist.p, dev.stream));
+    HIP_TRY(launch_design_select(w.a, dev.stream));
+    if (pair_hist) HIP_TRY(launch_design_hist(w.a, w.pair.p, dev.stream));
+    int ctl[5];
+    HIP_TRY(hipMemcpyAsync(ctl, w.ctl.p, sizeof(ctl), hipMemcpyDeviceToHost, dev.stream));
+    HIP_TRY(hipStreamSynchronize(dev.stream));
+    if (ctl[DESIGN_BAD]) return fail(ADX_EINVAL, "adx_select_designs: a character outside ACGU / acgu");
+    const size_t nd = size_t(ctl[2]);
+    HIP_TRY(hipMemcpyAsync(leaders, w.leaders.p, nd * sizeof(int32_t), hipMemcpyDeviceToHost, dev.stream));
+    HIP_TRY(hipMemcpyAsync(sizes, w.sizes.p, nd * sizeof(int32_t), hipMemcpyDeviceToHost, dev.stream));
+    if (member_of)
+        HIP_TRY(hipMemcpyAsync(member_of, w.member_of.p, size_t(M) * sizeof(int32_t), hipMemcpyDeviceToHost, dev.stream));
+    if (pair_hist)
+        HIP_TRY(hipMemcpyAsync(pair_hist, w.pair.p, (size_t(N) + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, dev.stream));
+    HIP_TRY(hipStreamSynchronize(dev.stream));
+    *n_designs = int(nd);
+    return ADX_OK;
+}
+
+extern "C" adx_status adx_record_designs(adx_ctx *c, int window, int radius, int max_designs, int *n_designs,
+                                         int32_t *walkers, int64_t *steps, double *scores, char *seqs, int32_t *sizes,
+                                         int32_t *n_walkers, int64_t *n_picks_total, int64_t *pair_hist) {
+    if (!c || !n_designs) return fail(ADX_EINVAL, "adx_record_designs: null argument");
+    auto &rec = c->rec;
+    if (!rec.on) return fail(ADX_ESTATE, "adx_record_designs before adx_record_begin");
+    if (rec.broken)
+        return fail(ADX_ESTATE, "adx_record_designs: the record is broken (walkers initialised or imported during it, "
+                                "or a failed adx_run_steps); begin a new one");
+    if (rec.rows <= 0) return fail(ADX_ESTATE, "adx_record_designs: no step recorded yet");
+    Problem &pb = c->pb;
+    const int W = rec.W, S = rec.rows, N = pb.Nraw;
+    if (window < 1) return fail(ADX_EINVAL, "adx_record_designs: window %d < 1", window);
+    adx_status s = design_args_ok("adx_record_designs", N, radius, max_designs);
+    if (s) return s;
+    const int cap = (S - 1) / window + 1;
+    const size_t O = size_t(W) * size_t(cap);
+    if (O > size_t(0x7fffffff))
+        return fail(ADX_EINVAL, "adx_record_designs: %d walkers x %d picks exceed 2^31 - 1 entries", W, cap);
+    // the picks and their sequences, as adx_record_picks makes them, left on the device
+    DevBuf<int> dn, bad, doff, dtotal;
+    DevBuf<int32_t> dst;
+    DevBuf<double> dps;
+    DevBuf<char> dseq;
+    DevBuf<uint64_t> keys;
+    MEM_TRY(dn.alloc(size_t(W)));
+    MEM_TRY(doff.alloc(size_t(W)));
+    MEM_TRY(dtotal.alloc(1));
+    MEM_TRY(dst.alloc(O));
+    MEM_TRY(dps.alloc(O));
+    MEM_TRY(dseq.alloc(O * size_t(N)));
+    HIP_TRY(hipMemsetAsync(dst.p, 0xff, O * sizeof(int32_t), pb.stream));
+    s = pick_device(rec.cur.p, W, S, window, cap, keys, bad, dn.p, dst.p, dps.p, pb.stream);
+    if (s) return s;
+    ReplayArgs ra = record_replay_args(c);
+    ra.n_picks = dn.p;
+    ra.steps = dst.p;
+    ra.cap = cap;
+    ra.seqs = dseq.p;
+    ra.counts = nullptr;
+    HIP_TRY(launch_traj_replay(ra, pb.stream));
+    HIP_TRY(launch_design_offsets(dn.p, W, doff.p, dtotal.p, pb.stream));
+    int M = 0;
+    HIP_TRY(hipMemcpyAsync(&M, dtotal.p, sizeof(int), hipMemcpyDeviceToHost, pb.stream));
+    HIP_TRY(hipStreamSynchronize(pb.stream));
+    keys.reset();
+    if (n_picks_total) *n_picks_total = M;
+    if (pair_hist) std::fill(pair_hist, pair_hist + N + 1, int64_t(0));
+    *n_designs = 0;
+    c->design_select_ms = c->design_hist_ms = 0.0;
+    if (M == 0) return ADX_OK;   // no walker has a pick
+    const int K = std::min(max_designs, M);
+    DesignWork w;
+    DevBuf<int32_t> src_of, dwalk, drow, dnw;
+    DevBuf<double> dsc;
+    DevBuf<char> dlead;
+    s = w.alloc(M, N, radius, K, pair_hist != nullptr, pb.stream);
+    if (s) return s;
+    MEM_TRY(src_of.alloc(size_t(M)));
+    MEM_TRY(dwalk.alloc(size_t(K)));
+    MEM_TRY(drow.alloc(size_t(K)));
+    MEM_TRY(dnw.alloc(size_t(K)));
+    MEM_TRY(dsc.alloc(size_t(K)));
+    MEM_TRY(dlead.alloc(size_t(K) * N));
+    HIP_TRY(hipMemsetAsync(dnw.p, 0, size_t(K) * sizeof(int32_t), pb.stream));
+    Events3 ev;
+    for (auto &x : ev.e) HIP_TRY(hipEventCreate(&x));
+    HIP_TRY(hipEventRecord(ev.e[0], pb.stream));
+    HIP_TRY(launch_design_pack(dseq.p, dps.p, N, int(O), dn.p, doff.p, cap, M, w.planes.p, w.keys.p, w.idx.p, src_of.p,
+                               w.a.flags, pb.stream));
+    HIP_TRY(launch_design_order(w.keys.p, w.idx.p, w.keys_tmp.p, w.idx_tmp.p, M, w.hist.p, pb.stream));
+    HIP_TRY(launch_design_select(w.a, pb.stream));
+    HIP_TRY(launch_design_walkers(w.a, src_of.p, cap, dnw.p, pb.stream));
+    HIP_TRY(launch_design_gather(w.a, src_of.p, cap, dst.p, dps.p, dseq.p, dwalk.p, drow.p, dsc.p, dlead.p, pb.stream));
+    HIP_TRY(hipEventRecord(ev.e[1], pb.stream));
+    if (pair_hist) HIP_TRY(launch_design_hist(w.a, w.pair.p, pb.stream));
+    HIP_TRY(hipEventRecord(ev.e[2], pb.stream));
+    int ctl[5];
+    HIP_TRY(hipMemcpyAsync(ctl, w.ctl.p, sizeof(ctl), hipMemcpyDeviceToHost, pb.stream));
+    HIP_TRY(hipStreamSynchronize(pb.stream));
+    if (ctl[DESIGN_BAD]) return fail(ADX_EINVAL, "adx_record_designs: a recorded sequence holds a base outside ACGU");
+    const size_t nd = size_t(ctl[2]);
+    std::vector<int32_t> rows(nd);
+    if (walkers) HIP_TRY(hipMemcpyAsync(walkers, dwalk.p, nd * sizeof(int32_t), hipMemcpyDeviceToHost, pb.stream));
+    if (steps) HIP_TRY(hipMemcpyAsync(rows.data(), drow.p, nd * sizeof(int32_t), hipMemcpyDeviceToHost, pb.stream));
+    if (scores) HIP_TRY(hipMemcpyAsync(scores, dsc.p, nd * sizeof(double), hipMemcpyDeviceToHost, pb.stream));
+    if (seqs) HIP_TRY(hipMemcpyAsync(seqs, dlead.p, nd * size_t(N), hipMemcpyDeviceToHost, pb.stream));
+    if (sizes) HIP_TRY(hipMemcpyAsync(sizes, w.sizes.p, nd * sizeof(int32_t), hipMemcpyDeviceToHost, pb.stream));
+    if (n_walkers) HIP_TRY(hipMemcpyAsync(n_walkers, dnw.p, nd * sizeof(int32_t), hipMemcpyDeviceToHost, pb.stream));
+    if (pair_hist)
+        HIP_TRY(hipMemcpyAsync(pair_hist, w.pair.p, (size_t(N) + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, pb.stream));
+    HIP_TRY(hipStreamSynchronize(pb.stream));
+    if (steps)
+        for (size_t d = 0; d < nd; d++) steps[d] = rec.step0 + rows[d];
+    *n_designs = int(nd);
+    float a = 0.f, b = 0.f;
+    HIP_TRY(hipEventElapsedTime(&a, ev.e[0], ev.e[1]));
+    HIP_TRY(hipEventElapsedTime(&b, ev.e[1], ev.e[2]));
+    c->design_select_ms = a;
+    c->design_hist_ms = b;
+    return ADX_OK;
+}
+
+extern "C" adx_status adx_last_design_ms(const adx_ctx *c, double *select_ms, double *hist_ms) {
+    if (!c || !select_ms || !hist_ms) return fail(ADX_EINVAL, "adx_last_design_ms: null argument");
+    *select_ms = c->design_select_ms;
+    *hist_ms = c->design_hist_ms;
     return ADX_OK;
 }

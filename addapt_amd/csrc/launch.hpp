@@ -184,6 +184,47 @@ hipError_t launch_autocorr_lags(const uint64_t *planes, int nw, int P, int kept,
                                 unsigned long long *pos_matches, unsigned long long *walker_matches,
                                 hipStream_t stream);
 
+// ---- design_select.hip: distinct designs by greedy Hamming selection (design_select_core.hpp).
+// M entries are packed into two bit planes, planes[(plane * ds_words(N) + word) * M + entry],
+// ordered by a radix sort of (key, entry) and selected in rank order; everything runs on one
+// stream and reads the counts it needs (flags, state) from the device.  The caller zeroes
+// flags, state and sizes, sets member_rank to -1 and checks N <= 255, radius >= 0, 1 <= K <= M.
+constexpr int DESIGN_BAD = 0, DESIGN_FINITE = 1;   // flags: a bad character seen; entries with a finite score
+int design_sort_blocks(int M);                     // hist = 256 * design_sort_blocks(M) ints
+// offset[w] = the sum of max(n_picks[v], 0) over v < w, *total = over all walkers
+hipError_t launch_design_offsets(const int *n_picks, int W, int *offset, int *total, hipStream_t stream);
+// Sequences seqs[slot * N ..] with scores[slot].  n_picks == nullptr: slot = entry, n_slots = M.
+// Else slot = walker * cap + k is an entry iff k < n_picks[walker], entry offset[walker] + k, and
+// src_of[entry] = slot.  keys = the sort keys, idx = the identity, both M long.
+hipError_t launch_design_pack(const char *seqs, const double *scores, int N, int n_slots, const int *n_picks,
+                              const int *offset, int cap, int M, uint64_t *planes, uint64_t *keys, int32_t *idx,
+                              int32_t *src_of, int *flags, hipStream_t stream);
+// sorts (keys, idx) in place; keys_tmp / idx_tmp: M each
+hipError_t launch_design_order(uint64_t *keys, int32_t *idx, uint64_t *keys_tmp, int32_t *idx_tmp, int M, int *hist,
+                               hipStream_t stream);
+struct DesignArgs {
+    int M, N, radius, K;
+    const uint64_t *planes;     // entry order
+    const int32_t *order;       // [M] rank -> entry (launch_design_order's idx)
+    uint64_t *rank_planes;      // as planes, in rank order (written by select, read by hist)
+    int *flags;                 // [2]
+    int *state;                 // [3]; state[0] = the number of designs
+    int32_t *member_rank;       // [M] by rank
+    int32_t *leader_rank;       // [K]
+    uint64_t *lead_planes;      // [2 * ds_words(N) * K] the leaders' planes
+    int32_t *member_of;         // [M] by entry
+    int32_t *sizes, *leaders;   // [K]
+};
+hipError_t launch_design_select(const DesignArgs &a, hipStream_t stream);
+// after launch_design_select: pair_hist[N + 1], added to
+hipError_t launch_design_hist(const DesignArgs &a, unsigned long long *pair_hist, hipStream_t stream);
+// the record's glue: n_walkers[K] added to; the leaders' walker, record row, score and sequence
+hipError_t launch_design_walkers(const DesignArgs &a, const int32_t *src_of, int cap, int32_t *n_walkers,
+                                 hipStream_t stream);
+hipError_t launch_design_gather(const DesignArgs &a, const int32_t *src_of, int cap, const int32_t *pick_rows,
+                                const double *pick_scores, const char *pick_seqs, int32_t *walkers, int32_t *rows,
+                                double *scores, char *seqs, hipStream_t stream);
+
 // ---- mc_step.hip
 hipError_t launch_steps(const KArgs &ka, const StepArgs &st, hipStream_t stream, hipEvent_t *evs);
 hipError_t launch_rescore(const KArgs &ka, const StepArgs &st, double *tv, hipStream_t stream);

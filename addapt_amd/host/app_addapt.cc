@@ -5,6 +5,7 @@
 //                      [-i <steps>] [--walkers <W>] [--gpu <id>] [--params <file>]
 //                      [--reference-loop] [--picks <path>] [--pick-window <steps>|auto]
 //                      [--autocorr <path>] [--autocorr-lag <steps>] [--autocorr-discard <steps>]
+//                      [--designs <path>] [--design-radius <mutations>] [--max-designs <num>]
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -60,6 +61,17 @@ static const char USAGE[] =
     "    The largest lag (clipped to the kept steps - 1).\n"
     "  --autocorr-discard <steps>             [default: 100]\n"
     "    Steps dropped from the start of every trajectory (equilibration).\n"
+    "  --designs <path>\n"
+    "    With --walkers: record every walker's trajectory on the GPU, pick as --picks\n"
+    "    does (with the run's pick window) and write the distinct designs among all\n"
+    "    walkers' picks: best score first, a pick leads a new design if no earlier\n"
+    "    leader is within the design radius of it, and else counts towards the first\n"
+    "    leader that is.  '#' lines with the numbers of picks and designs, the radius\n"
+    "    and the pick pairs per distance (d:count), then one row per design: its\n"
+    "    leader, the picks it covers and the distinct walkers among them.\n"
+    "  --design-radius <mutations>            [default: 3]\n"
+    "    Leaders are more than this many mutations apart (0: exact duplicates only).\n"
+    "  --max-designs <num>                    [default: 100]\n"
     "  --gpu <id>                             [default: 0]\n"
     "  --params <file>  Energy parameters (ViennaRNA 2.0 format).\n"
     "  --reference-loop  Run the reference's single-walker loop (one GPU fold call\n"
@@ -122,10 +134,29 @@ static void write_autocorr(const std::string &path, const Autocorr &ac) {
     std::fclose(f);
 }
 
+// The distinct designs of a batched run: '#' lines, then one row per design.
+static void write_designs(const std::string &path, const BatchResult &res, int radius,
+                          const std::vector<uint32_t> &seeds) {
+    FILE *f = std::fopen(path.c_str(), "w");
+    if (!f) throw std::string("couldn't open '" + path + "' for writing");
+    std::fprintf(f, "# Num Picks: %lld\n# Num Designs: %zu\n# Radius: %d\n# Pair Distances:", (long long)res.n_picks,
+                 res.designs.size(), radius);
+    for (size_t d = 0; d < res.pair_hist.size(); d++)
+        if (res.pair_hist[d]) std::fprintf(f, " %zu:%lld", d, (long long)res.pair_hist[d]);
+    std::fprintf(f, "\ndesign\twalker\tseed\tstep\tscore\tpicks\twalkers\tseq\n");
+    for (size_t d = 0; d < res.designs.size(); d++) {
+        const Design &x = res.designs[d];
+        std::fprintf(f, "%zu\t%d\t%u\t%lld\t%.17g\t%d\t%d\t%s\n", d, x.walker, seeds[size_t(x.walker)],
+                     (long long)x.step, x.score, x.picks, x.walkers, x.seq.c_str());
+    }
+    std::fclose(f);
+}
+
 int main(int argc, char **argv) {
     std::vector<std::string> configs;
-    std::string temp, out = "traj.tsv", params, picks, autocorr;
+    std::string temp, out = "traj.tsv", params, picks, autocorr, designs;
     int num = 100, interval = 1, walkers = 1, gpu = 0, pick_window = 500, autocorr_lag = 500, autocorr_discard = 100;
+    int design_radius = 3, max_designs = 100;
     bool auto_window = false;
     unsigned long seed = 0;
     bool ref_loop = false;
@@ -153,6 +184,9 @@ int main(int argc, char **argv) {
             else if (a == "--autocorr") autocorr = val("--autocorr");
             else if (a == "--autocorr-lag") autocorr_lag = std::stoi(val("--autocorr-lag"));
             else if (a == "--autocorr-discard") autocorr_discard = std::stoi(val("--autocorr-discard"));
+            else if (a == "--designs") designs = val("--designs");
+            else if (a == "--design-radius") design_radius = std::stoi(val("--design-radius"));
+            else if (a == "--max-designs") max_designs = std::stoi(val("--max-designs"));
             else if (a == "--gpu") gpu = std::stoi(val("--gpu"));
             else if (a == "--params") params = val("--params");
             else if (a == "--reference-loop") ref_loop = true;
@@ -164,9 +198,13 @@ int main(int argc, char **argv) {
             return 1;
         }
         if (!picks.empty() && walkers <= 1) throw std::string("--picks needs --walkers <W> with W > 1");
-        if (!picks.empty() && !auto_window && pick_window < 1) throw std::string("--pick-window must be at least 1");
+        if (!designs.empty() && walkers <= 1) throw std::string("--designs needs --walkers <W> with W > 1");
+        const bool picking = !picks.empty() || !designs.empty();
+        if (picking && !auto_window && pick_window < 1) throw std::string("--pick-window must be at least 1");
+        if (!designs.empty() && design_radius < 0) throw std::string("--design-radius must not be negative");
+        if (!designs.empty() && max_designs < 1) throw std::string("--max-designs must be at least 1");
         if (!autocorr.empty() && walkers <= 1) throw std::string("--autocorr needs --walkers <W> with W > 1");
-        const bool correlating = !autocorr.empty() || (!picks.empty() && auto_window);
+        const bool correlating = !autocorr.empty() || (picking && auto_window);
         if (correlating && autocorr_lag < 1) throw std::string("--autocorr-lag must be at least 1");
         if (correlating && autocorr_discard < 0) throw std::string("--autocorr-discard must not be negative");
         if (!params.empty()) set_parameter_file(params);
@@ -182,8 +220,12 @@ int main(int argc, char **argv) {
             std::vector<uint32_t> seeds(walkers);
             for (int w = 0; w < walkers; w++) seeds[w] = uint32_t(seed + w);
             BatchOptions opt;
-            opt.pick_window = picks.empty() || auto_window ? 0 : pick_window;
-            opt.auto_window = !picks.empty() && auto_window;
+            opt.pick_window = !picking || auto_window ? 0 : pick_window;
+            opt.auto_window = picking && auto_window;
+            if (!designs.empty()) {
+                opt.design_radius = design_radius;
+                opt.max_designs = max_designs;
+            }
             opt.autocorr_lag = correlating ? autocorr_lag : 0;
             opt.autocorr_discard = correlating ? autocorr_discard : 0;
             auto res = mc->apply_batch(device, seeds, gpu, opt);
@@ -200,6 +242,7 @@ int main(int argc, char **argv) {
             std::fclose(f);
             if (!picks.empty()) write_picks(picks, res, seeds);
             if (!autocorr.empty()) write_autocorr(autocorr, res.autocorr);
+            if (!designs.empty()) write_designs(designs, res, design_radius, seeds);
             return 0;
         }
         *mc += std::make_shared<ProgressReporter>();

@@ -267,6 +267,9 @@ BatchResult MonteCarlo::apply_batch(DevicePtr device, const std::vector<uint32_t
     if (opt.autocorr_lag > 0 && steps_ > 0 && opt.autocorr_discard >= steps_)   // before the run, not after it
         throw string("apply_batch: autocorrelation discard " + std::to_string(opt.autocorr_discard) +
                      " leaves none of the " + std::to_string(steps_) + " steps");
+    if (opt.design_radius >= 0 && opt.pick_window <= 0 && !opt.auto_window)
+        throw string("apply_batch: designs are selected from the picks and need a pick window (pick_window > 0 or auto_window)");
+    if (opt.design_radius >= 0 && opt.max_designs < 1) throw string("apply_batch: max_designs must be at least 1");
     EngineSetup e;
     build_setup(*this, device, g, e);
     adx_ctx *raw = nullptr;
@@ -349,6 +352,20 @@ BatchResult MonteCarlo::apply_batch(DevicePtr device, const std::vector<uint32_t
                 const size_t o = size_t(w) * cap + k;
                 out[w].picks.push_back(Pick{w, psteps[o], pscores[o], string(&pseqs[o * N], N)});
             }
+    }
+    if (picking && opt.design_radius >= 0) {
+        const size_t K = size_t(opt.max_designs);
+        int nd = 0;
+        std::vector<int32_t> dw(K), dsz(K), dnw(K);
+        std::vector<int64_t> dsteps(K);
+        std::vector<double> dscores(K);
+        std::vector<char> dseqs(K * N);
+        out.pair_hist.assign(N + 1, 0);
+        gpu::check(adx_record_designs(ctx.get(), pick_window, opt.design_radius, opt.max_designs, &nd, dw.data(),
+                                      dsteps.data(), dscores.data(), dseqs.data(), dsz.data(), dnw.data(), &out.n_picks,
+                                      out.pair_hist.data()));
+        for (int d = 0; d < nd; d++)
+            out.designs.push_back(Design{dw[d], dsteps[d], dscores[d], string(&dseqs[size_t(d) * N], N), dsz[d], dnw[d]});
     }
     if (picking || correlating) gpu::check(adx_record_end(ctx.get()));
     for (int w = 0; w < W; w++) {

@@ -89,6 +89,7 @@ EXPORTS = [
     "adx_last_ensemble_ms",
     "adx_pick_scores", "adx_record_begin", "adx_record_end", "adx_record_picks", "adx_last_pick_ms",
     "adx_autocorr_codes", "adx_record_autocorr", "adx_last_autocorr_ms", "adx_autocorr_time",
+    "adx_select_designs", "adx_record_designs", "adx_last_design_ms",
 ]
 
 _lib = None
@@ -176,6 +177,14 @@ def lib():
         L.adx_last_autocorr_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.adx_autocorr_time.argtypes = [C.POINTER(C.c_int64), C.c_int, C.c_int64, C.c_int64, C.c_double,
                                         C.POINTER(C.c_int)]
+        L.adx_select_designs.argtypes = [C.c_int, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_double), C.c_int, C.c_int,
+                                         C.POINTER(C.c_int), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                         C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+        L.adx_record_designs.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int),
+                                         C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.c_char_p,
+                                         C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64),
+                                         C.POINTER(C.c_int64)]
+        L.adx_last_design_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         _lib = L
     return _lib
 
@@ -246,6 +255,45 @@ def autocorr_time(matches, n_series, kept_steps, baseline):
     _check(lib().adx_autocorr_time(m.ctypes.data_as(C.POINTER(C.c_int64)), len(m) - 1, n_series, kept_steps,
                                    baseline, C.byref(tau)))
     return tau.value
+
+
+def select_designs(seqs, scores, radius, max_designs=None, device=0, with_hist=True):
+    """Distinct designs among scored sequences by greedy Hamming selection
+    (adx_select_designs).  seqs: strings of one length over ACGU / acgu, or an
+    (entries, length) array of such characters (uint8 or S1); scores: a float per
+    entry.  Best score first (ties: the lower index; non-finite scores take no
+    part), an entry leads a new design iff no earlier leader is within `radius`
+    mutations of it, else it joins the lowest-numbered leader within `radius`; at
+    most max_designs designs (default: as many as entries).  A dict: leaders
+    (entry index per design) and sizes (entries covered), int32 of n_designs;
+    member_of (entries,) int32, -1 for none; pair_hist (length + 1,) int64, the
+    unordered pairs of finite-score entries per distance (None without with_hist)."""
+    if isinstance(seqs, np.ndarray) and seqs.ndim == 2:
+        ch = np.ascontiguousarray(seqs).view(np.uint8)
+        M, N = ch.shape
+        buf = ch.tobytes()
+    else:
+        seqs = [_b(s) for s in seqs]
+        M, N = len(seqs), (len(seqs[0]) if seqs else 0)
+        if any(len(s) != N for s in seqs):
+            raise ValueError("select_designs: sequences of different lengths")
+        buf = b"".join(seqs)
+    sc = np.ascontiguousarray(scores, np.float64).reshape(-1)
+    if len(sc) != M:
+        raise ValueError("select_designs: %d scores for %d sequences" % (len(sc), M))
+    if max_designs is None:
+        max_designs = max(M, 1)
+    K = max(max_designs, 1)
+    n = C.c_int()
+    lead, size = np.zeros(K, np.int32), np.zeros(K, np.int32)
+    member = np.zeros(max(M, 1), np.int32)
+    hist = np.zeros(max(N, 0) + 1, np.int64) if with_hist else None
+    i32 = C.POINTER(C.c_int32)
+    _check(lib().adx_select_designs(device, M, N, buf, sc.ctypes.data_as(C.POINTER(C.c_double)), radius, max_designs,
+                                    C.byref(n), lead.ctypes.data_as(i32), size.ctypes.data_as(i32),
+                                    member.ctypes.data_as(i32),
+                                    hist.ctypes.data_as(C.POINTER(C.c_int64)) if with_hist else None))
+    return dict(leaders=lead[:n.value].copy(), sizes=size[:n.value].copy(), member_of=member[:M], pair_hist=hist)
 
 
 class Params:
@@ -623,6 +671,36 @@ class Engine:
             baseline, tau, pooled = 1.0, 0, np.ones(L)
         return dict(pos_matches=pm, walker_matches=wm[:W], base_counts=bc, outcome_counts=oc[:W], changeable=ch,
                     kept_steps=kept, baseline=baseline, pooled=pooled, tau=tau)
+
+    def designs(self, window, radius, max_designs=100):
+        """(designs, pair_hist, n_picks): the distinct designs among the picks of the
+        steps recorded so far (adx_record_designs).  The entries are what
+        picks(window) returns, walker-major; best score first, a pick leads a new
+        design iff no earlier leader is within `radius` mutations of it.  Each design
+        is (walker, step, score, sequence, size, n_walkers) of its leader, size the
+        picks it covers and n_walkers the distinct walkers among them; pair_hist is
+        the (N + 1,) int64 count of pick pairs per distance, n_picks the entries."""
+        N, K = self.N, max(max_designs, 1)
+        n, total = C.c_int(), C.c_int64()
+        wk, sz, nw = np.zeros(K, np.int32), np.zeros(K, np.int32), np.zeros(K, np.int32)
+        st, sc = np.zeros(K, np.int64), np.zeros(K, np.float64)
+        buf = C.create_string_buffer(K * N + 1)
+        hist = np.zeros(N + 1, np.int64)
+        i32, i64 = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+        _check(lib().adx_record_designs(self.ptr, window, radius, max_designs, C.byref(n), wk.ctypes.data_as(i32),
+                                        st.ctypes.data_as(i64), sc.ctypes.data_as(C.POINTER(C.c_double)), buf,
+                                        sz.ctypes.data_as(i32), nw.ctypes.data_as(i32), C.byref(total),
+                                        hist.ctypes.data_as(i64)))
+        raw = buf.raw
+        out = [(int(wk[d]), int(st[d]), float(sc[d]), raw[d * N:(d + 1) * N].decode(), int(sz[d]), int(nw[d]))
+               for d in range(n.value)]
+        return out, hist, total.value
+
+    def last_design_ms(self):
+        """(selection ms, all-pairs histogram ms) of the last designs() call, from HIP events."""
+        a, b = C.c_double(), C.c_double()
+        _check(lib().adx_last_design_ms(self.ptr, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def last_autocorr_ms(self):
         """(plane packing ms, lag kernel ms) of the last autocorr() call, from HIP events."""

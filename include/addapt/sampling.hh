@@ -178,11 +178,26 @@ struct Autocorr {
     double outcome_share[4] = {0, 0, 0, 0};   ///< reject, accept worsened / unchanged / improved over the kept steps
 };
 
+/// one distinct design among all walkers' picks (adx_record_designs): its
+/// leader, the best pick no earlier leader is within the radius of, and what
+/// it covers
+struct Design {
+    int walker;          ///< the leader's walker,
+    int64_t step;        ///< 0-based step,
+    double score;        ///< score
+    std::string seq;     ///< and sequence
+    int picks;           ///< the picks within the radius of the leader that no earlier design took
+    int walkers;         ///< the distinct walkers among them: how often the design was found independently
+};
+
 /// the walkers' results; with a pick window also how often A, C, G, U stand at
 /// each position over all walkers' picks (base_counts[4 * position + base])
 struct BatchResult : std::vector<WalkerResult> {
     std::vector<int64_t> base_counts;
     Autocorr autocorr;                 ///< filled with BatchOptions::autocorr_lag > 0
+    std::vector<Design> designs;       ///< filled with BatchOptions::design_radius >= 0: best leader first
+    std::vector<int64_t> pair_hist;    ///< then [d], d = 0..N: the pairs of picks d mutations apart
+    int64_t n_picks = 0;               ///< and the number of picks the designs were selected from
 };
 
 /// what a batched run does besides stepping
@@ -192,6 +207,9 @@ struct BatchOptions {
                                 ///< if it is below 1 (not decayed, or nothing changed) with 500, warning on stderr
     int autocorr_lag = 0;       ///< > 0: the autocorrelation up to this lag (clipped to the kept steps - 1)
     int autocorr_discard = 0;   ///< steps dropped from the start (equilibration); must be below the number of steps
+    int design_radius = -1;     ///< >= 0: the distinct designs among the picks, leaders more than this many
+                                ///< mutations apart (needs a pick window, fixed or automatic)
+    int max_designs = 100;      ///< at most this many designs
 };
 
 class MonteCarlo {

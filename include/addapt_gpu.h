@@ -461,6 +461,71 @@ adx_status adx_last_autocorr_ms(const adx_ctx *ctx, double *pack_ms, double *lag
 adx_status adx_autocorr_time(const int64_t *matches, int max_lag, int64_t n_series, int64_t kept_steps,
                              double baseline, int *tau);
 
+/* ------------------------------------------------------------------------
+ * Distinct designs from scored sequences on the device: the sequence-space
+ * twin of the pick rule (picks are the best steps at least `window` steps
+ * apart in time, designs the best entries more than `radius` mutations apart
+ * in sequence).  For M entries (N bases A, C, G, U in either case, and a
+ * score), a radius r >= 0 and a cap K >= 1:
+ *   distance   the Hamming distance, bases compared case-insensitively
+ *   order      score descending (==: -0.0 ties with +0.0), ties by the lower
+ *              entry index; an entry with a non-finite score takes no part
+ *              (member_of = -1, counted nowhere)
+ *   selection  while fewer than K designs exist and an uncovered entry is
+ *              left: the first uncovered entry in order becomes the leader of
+ *              design d = 0, 1, ..., and every uncovered entry within r of it,
+ *              itself included, is covered by d (member_of = d).  So an entry
+ *              leads iff no earlier leader is within r of it, and otherwise
+ *              belongs to the lowest-numbered leader within r; entries still
+ *              uncovered when K is reached keep -1.  r = 0 removes exact
+ *              duplicates; r >= N makes one design.
+ *   pair_hist  [d], d = 0..N: the unordered pairs of finite-score entries at
+ *              distance d; the sum is F (F - 1) / 2 for F such entries.  It
+ *              shows how concentrated the entries are and what radius makes
+ *              sense, as the autocorrelation does for the window.
+ * All of it is integer work: equal inputs give equal bytes.
+ * ---------------------------------------------------------------------- */
+
+/* Stateless: seqs = n_seqs * length chars, no terminators; scores[n_seqs].
+ * leaders, sizes = max_designs int32 each, the first *n_designs valid: the
+ * leader's entry index and the number of entries the design covers.
+ * member_of = n_seqs int32 and pair_hist = (length + 1) int64 are optional
+ * (NULL; the all-pairs pass is skipped without pair_hist).  n_seqs < 1, length
+ * outside 1..255, radius < 0, max_designs < 1 or a character outside
+ * ACGU / acgu: ADX_EINVAL. */
+adx_status adx_select_designs(int device, int n_seqs, int length, const char *seqs,
+                              const double *scores, int radius, int max_designs,
+                              int *n_designs, int32_t *leaders, int32_t *sizes,
+                              int32_t *member_of, int64_t *pair_hist);
+
+/* The same over the picks of the steps recorded so far (adx_record_begin):
+ * the entries are what adx_record_picks returns for `window` (with its own
+ * cap, ceil(recorded steps / window)), walker-major and then by ascending
+ * step, so equal scores go to the lower walker and then the lower step;
+ * walkers with a count of -1 contribute nothing.  Picks, sequences and the
+ * selection stay on the device; only the designs and the histogram cross.
+ * Per design, max_designs entries each, the first *n_designs valid: walkers,
+ * steps (global 0-based, as adx_record_picks), scores and seqs (max_designs * N
+ * chars, no terminators) of its leader; sizes, the picks it covers; n_walkers,
+ * the distinct walkers among them (a pick counts iff no earlier pick of its
+ * walker has the same design: the evidence of independent rediscovery).
+ * *n_picks_total = the number of entries; pair_hist = (N + 1) int64.  Every
+ * output but n_designs is optional (NULL).  A record in which no walker has a
+ * pick gives *n_designs = 0 and ADX_OK.  window < 1, radius < 0 or
+ * max_designs < 1: ADX_EINVAL; before adx_record_begin, with nothing recorded
+ * or on a broken record: ADX_ESTATE, as adx_record_picks.  May be repeated and
+ * interleaved with adx_record_picks and adx_record_autocorr; touches neither
+ * the walkers nor the record. */
+adx_status adx_record_designs(adx_ctx *ctx, int window, int radius, int max_designs,
+                              int *n_designs, int32_t *walkers, int64_t *steps,
+                              double *scores, char *seqs, int32_t *sizes,
+                              int32_t *n_walkers, int64_t *n_picks_total, int64_t *pair_hist);
+/* Device time (ms, HIP events) of the context's last adx_record_designs:
+ * packing, ordering and selecting (with the leaders' gather), and the
+ * all-pairs histogram (0 without pair_hist).  The picking and replay before
+ * them are not included. */
+adx_status adx_last_design_ms(const adx_ctx *ctx, double *select_ms, double *hist_ms);
+
 /* Variant v of the score: which (context, condition, macrostate or -1). */
 adx_status adx_variant_desc(const adx_ctx *ctx, int v, int *context, int *condition,
                             int *macrostate);
