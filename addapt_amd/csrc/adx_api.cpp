@@ -984,6 +984,15 @@ static adx_status fold_one(adx_fold *f, int mode, Problem &pb, DevBuf<uint8_t> &
                 if (s) return s;
                 continue;
             }
+            // +inf on the assumed scale is also what a constrained ensemble of positive energy gives
+            // once its weight times sigma^N falls below FP32 (about 64 kcal/mol above N * g0): fold
+            // once more on the mildest scale, which a finite first fold would have chosen for it
+            if (attempt == 0 && !std::isfinite(g) && pb.g0 < -0.05) {
+                pb.g0 = -0.05;
+                s = pb.upload_scaled();
+                if (s) return s;
+                continue;
+            }
             break;
         }
         pb.g0 *= 2.0;
