@@ -20,6 +20,7 @@
 #include "dev_types.hpp"
 #include "energy.hpp"
 #include "launch.hpp"
+#include "loop_codetab_core.hpp"
 #include "traj_autocorr_core.hpp"
 
 using namespace adx;
@@ -417,6 +418,7 @@ struct Problem {
     // MFE: packed 16-bit copies of the energy tables (fold_rows.hip MinPlus16)
     DevBuf<DevTables> dT16;
     DevBuf<DevScaled> dX16;
+    DevBuf<uint16_t> dLoop16;    // T16's 1x1 .. 2x2 energies by code pair (loop_codetab_core.hpp)
     DevBuf<int> dOvf;
     bool mfe16 = false;
     bool mfe_cells_ok = false;   // Ninio saturated from |n1-n2| = 5 on, MLbase >= 0 (mfe_cells.hip)
@@ -487,6 +489,7 @@ struct Problem {
         ka.T16 = mfe16 ? dT16.p : nullptr;
         ka.X16 = mfe16 ? dX16.p : nullptr;
         ka.ovf = mfe16 ? dOvf.p : nullptr;
+        ka.loop16 = mfe16 ? dLoop16.p : nullptr;
         ka.mfe_cells_ok = mfe16 && mfe_cells_ok ? 1 : 0;
         const bool st = state_on && dTab.p && !std::getenv("ADX_NO_INCR");
         ka.tab = st ? dTab.p : nullptr;
@@ -553,6 +556,14 @@ struct Problem {
                     X16->ku16[u][f] = f < 6 ? ((u >= 6 && u <= 30) ? il[u] + nin[f] : 0u)
                                     : f == 6 ? ct[CT_FB + u] : (u >= 1 ? ct[CT_F1N + u - 1] : 0x7FFF7FFFu);
         }
+        // the 1x1 .. 2x2 energies by code pair (mfe_pair.hip bcell_tables)
+        std::vector<uint16_t> loop16(LCT_ALLOC);
+        static_assert(sizeof(float) == sizeof(uint32_t), "packed words in the tables' floats");
+        if (!loop_codetab_build(reinterpret_cast<const uint32_t *>(&T16->int11[0][0][0][0]),
+                                reinterpret_cast<const uint32_t *>(&T16->int21[0][0][0][0][0]),
+                                reinterpret_cast<const uint32_t *>(&T16->int22[0][0][0][0][0][0]), loop16.data()))
+            return ADX_OK;   // FP32 MinPlus only
+        HIP_TRY(dLoop16.upload(loop16.data(), loop16.size(), stream));
         HIP_TRY(dT16.upload(T16.get(), 1, stream));
         HIP_TRY(dX16.upload(X16.get(), 1, stream));
         HIP_TRY(hipStreamSynchronize(stream));

@@ -212,6 +212,9 @@ struct KArgs {
     // are combined by the step's tail (mc_step.hip accept_walker), not by a
     // combine_kernel launch of their own
     int defer_comb;
+    // MFE: the 1x1 .. 2x2 interior-loop energies of T16 by code pair
+    // (loop_codetab_core.hpp; mfe_pair.hip bcell_tables)
+    const uint16_t *loop16;
 };
 
 // Monte Carlo state (device, read/write).

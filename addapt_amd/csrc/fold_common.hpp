@@ -36,6 +36,38 @@ __device__ __forceinline__ int off(int dd, int N) { return ((dd - 4) * (2 * N - 
 
 __device__ __forceinline__ int uni(int x) { return __builtin_amdgcn_readfirstlane(x); }
 
+// Loads and stores of device memory through a pointer typed to the global
+// address space at the dereference: global_load / global_store, which count on
+// vmcnt alone.  A pointer the compiler cannot trace to a kernel argument (one
+// rebuilt from words that mfe_pair.hip's loop reads again from the argument
+// segment) is a generic pointer, and an access through it is a flat
+// instruction, which counts on lgkmcnt as well: every `s_waitcnt lgkmcnt(0)`
+// after an LDS batch then also waits for the loads from L2 / HBM still in flight.
+// Where the compiler already knows the address space the code is the same.
+// (uint2 / uint4 go as vectors of words: 8- and 16-byte accesses)
+template <class T>
+struct gmem_word {
+    using type = T;
+};
+template <>
+struct gmem_word<uint2> {
+    typedef uint32_t type __attribute__((ext_vector_type(2)));
+};
+template <>
+struct gmem_word<uint4> {
+    typedef uint32_t type __attribute__((ext_vector_type(4)));
+};
+template <class T>
+__device__ __forceinline__ T gld(const T *p) {
+    typedef __attribute__((address_space(1))) const typename gmem_word<T>::type g_t;
+    return __builtin_bit_cast(T, *(g_t *)(p));   // generic -> global address space
+}
+template <class T, class V>
+__device__ __forceinline__ void gst(T *p, V v) {
+    typedef __attribute__((address_space(1))) typename gmem_word<T>::type g_t;
+    *(g_t *)(p) = __builtin_bit_cast(typename gmem_word<T>::type, T(v));
+}
+
 // Workgroup barrier ordering LDS only (the fold's waves share nothing else
 // inside its diagonal loop): outstanding global loads are not drained, so a
 // prefetch issued before the barrier completes in the shadow of the next
@@ -77,13 +109,13 @@ struct WalkerRef {
 template <class K>
 __device__ __forceinline__ WalkerRef walker_ref(const K &ka, const int *mask, int wb) {
     WalkerRef r;
-    r.w = ka.order ? ka.order[wb] : wb;
+    r.w = ka.order ? gld(ka.order + wb) : wb;
     const int w = r.w;
-    const int mk = mask ? mask[w] : 1;
-    r.cur = ka.tab ? int(ka.cur_slot[w]) : 0;
-    r.valid = ka.tab ? ka.tab_valid[w] != 0 : false;
-    r.c0 = ka.chg ? ka.chg[2 * w] : -1;
-    r.c1 = ka.chg ? ka.chg[2 * w + 1] : -1;
+    const int mk = mask ? gld(mask + w) : 1;
+    r.cur = ka.tab ? int(gld(ka.cur_slot + w)) : 0;
+    r.valid = ka.tab ? gld(ka.tab_valid + w) != 0 : false;
+    r.c0 = ka.chg ? gld(ka.chg + 2 * w) : -1;
+    r.c1 = ka.chg ? gld(ka.chg + 2 * w + 1) : -1;
     r.on = mk == 1;
     return r;
 }

@@ -15,6 +15,7 @@
 
 #include "dev_types.hpp"
 #include "fold_common.hpp"
+#include "loop_codetab_core.hpp"
 
 namespace adx {
 namespace {
@@ -106,7 +107,7 @@ struct BCell {                // per lane: the closing pair (i, i+d)
     int hb;                   // pair kernel (mfe_pair.hip): 1 on the lanes of the step's second diagonal
     int ea, eb, ctb;          // sliced blocks: the slice's edge shapes n1 = ea + eb * u, their factor table
     u32 m23f;                 // 2x3: interior[5] + ninio + outer mismatch23
-    u32 t11, t12, t21, t22;   // prefetched 1x1 / 1x2 / 2x1 / 2x2 table energies
+    u32 t11, t12, t21, t22;   // prefetched 1x1 / 1x2 / 2x1 / 2x2 table energies (mfe_pair.hip: the low half)
 };
 struct Acc {
     u32 s, g0, g1, b, n;      // specials; generic (+ outer mismatchI, even / odd u1); bulges (+ TermAU); 1xn (+ mismatch1n)
@@ -128,7 +129,7 @@ __device__ __forceinline__ BUni buni(const LT &L, const DevScaled *XS, int N) {
     U.aq = lds_addr(L.qbm);
     U.ac = lds_addr(L.cc);
     U.act = lds_addr(L.ct);
-    U.fs1 = gct[CT_FSM + 1];
+    U.fs1 = gld(gct + CT_FSM + 1);
     U.il = reinterpret_cast<const u32 *>(XS->il);
     U.nin = reinterpret_cast<const u32 *>(XS->nin);
     U.N = N;
@@ -179,35 +180,35 @@ __device__ __forceinline__ void bcell_slice(BCell &C, int r, int sh, uint32_t ae
     C.ctb = (r & 2) ? CT_ONEN : CT_BUL;
 }
 
+// the two 16-bit energies of a word, each to a packed apo | holo word
+__device__ __forceinline__ u32 lo2(u32 x) { return __builtin_amdgcn_perm(x, x, 0x05040504u); }
+__device__ __forceinline__ u32 hi2(u32 x) { return __builtin_amdgcn_perm(x, x, 0x07060706u); }
+
 // 1x1 .. 2x2 energies of cell (i, i + dd) from HBM (L2), used at the block end (the caller starts
-// them at INF16); p2, p3, p4: this wave's block reads loop size 2, 3, 4, um: the cell's largest.
+// them at INF16), 16 bits wide as loaded: the block widens them with lo2() where it uses them
+// (widened here, each load was waited for at once); p2, p3, p4: this wave's block reads loop size 2, 3, 4, um: the cell's largest.
+// E: the energies by code pair (loop_codetab_core.hpp, KArgs::loop16), E[k][oc][c] with the cell's
+// code oc and the inner pair's c as they stand: one multiply-add and one load per energy (indexing
+// int11 / int21 / int22 by the types and bases took the codes apart with / 5 and % 5, 50 VALU
+// instructions a step on the size-3 wave).
 // mfe_pair.hip only: mfe_cells.hip tests one bit per block and keeps its copy (this form: -1.9 % at N = 150)
 template <class LT>
-__device__ __forceinline__ void bcell_tables(BCell &C, const LT &L, const DevTables &T, int N, int dd, int i, int oc,
+__device__ __forceinline__ void bcell_tables(BCell &C, const LT &L, const uint16_t *E, int N, int dd, int i, int oc,
                                              int um, bool p2, bool p3, bool p4) {
-    const u32 *T11 = reinterpret_cast<const u32 *>(&T.int11[0][0][0][0]);
-    const u32 *T21 = reinterpret_cast<const u32 *>(&T.int21[0][0][0][0][0]);
-    const u32 *T22 = reinterpret_cast<const u32 *>(&T.int22[0][0][0][0][0][0]);
-    const int type = (oc * 41) >> 10, ty8 = type * 8;
-    const int si1 = (oc / 5) % 5, sj1 = oc % 5;
-    if (p2 && um >= 2) {
-        const int c2 = L.cc[off(dd - 4, N) + i + 1];
-        C.t11 = T11[((ty8 + ((c2 * 41) >> 10)) * 5 + si1) * 5 + sj1];
-    }
+    // byte offsets in 32 bits off the one uniform base: row oc by a 24-bit multiply, once per cell
+    const uint32_t ob = __umul24(uint32_t(oc), uint32_t(sizeof(uint16_t)) * LCT_CODES);
+    auto at = [&](int k, int c) {
+        const uint32_t o = ob + uint32_t(sizeof(uint16_t)) * uint32_t(loop_codetab_index(k, 0, c));
+        return u32(gld(reinterpret_cast<const uint16_t *>(reinterpret_cast<const char *>(E) + o)));
+    };
+    if (p2 && um >= 2) C.t11 = at(LCT_11, L.cc[off(dd - 4, N) + i + 1]);
     if (p3 && um >= 3) {
         const int o3 = off(dd - 5, N) + i;
         const int a2 = L.cc[o3 + 1], b2 = L.cc[o3 + 2];
-        const int ta = (a2 * 41) >> 10, tb = (b2 * 41) >> 10;
-        // 1x2: int21[type][t2][si1][sq1][sj1]; 2x1: int21[t2][type][sq1][si1][sp1]
-        C.t12 = T21[(((ty8 + ta) * 5 + si1) * 5 + (a2 / 5) % 5) * 5 + sj1];
-        C.t21 = T21[(((tb * 8 + type) * 5 + (b2 / 5) % 5) * 5 + si1) * 5 + b2 % 5];
+        C.t12 = at(LCT_12, a2);
+        C.t21 = at(LCT_21, b2);
     }
-    if (p4 && um >= 4) {
-        const int c2 = L.cc[off(dd - 6, N) + i + 2];
-        const int t2 = (c2 * 41) >> 10;
-        // int22[type][t2][si1][sp1][sq1][sj1]
-        C.t22 = T22[((((ty8 + t2) * 5 + si1) * 5 + c2 % 5) * 5 + (c2 / 5) % 5) * 5 + sj1];
-    }
+    if (p4 && um >= 4) C.t22 = at(LCT_22, L.cc[off(dd - 6, N) + i + 2]);
 }
 
 // a block's accumulators to the cell's partial minimum: the outer pair's terms,
@@ -300,6 +301,7 @@ template <class V, int NT, class LT>
 __device__ __forceinline__ int writeback_vectors(const LT &L, u32 *dp, size_t Cs, int C, int tid, bool &low) {
     constexpr int n = int(sizeof(V) / sizeof(u32));
     const int nv = C / n;   // n = 1, 2, 4: a shift
+    const uint32_t cs = uint32_t(Cs) / n;   // (the caller checked that Cs is a multiple of n)
     for (int k = tid; k < nv; k += NT) {
         const V a = reinterpret_cast<const V *>(L.qbm)[k];
         const V b = reinterpret_cast<const V *>(L.qm)[k];
@@ -311,9 +313,10 @@ __device__ __forceinline__ int writeback_vectors(const LT &L, u32 *dp, size_t Cs
 #pragma unroll
         for (int t = 0; t < 3 * n; t++) low |= mfe16_inexact(sv(e[t]));
         if (dp) {
-            reinterpret_cast<V *>(dp)[k] = a;
-            reinterpret_cast<V *>(dp + Cs)[k] = b;
-            reinterpret_cast<V *>(dp + 2 * Cs)[k] = c;
+            // (32-bit offsets from the slot: one base address for the three tables)
+            gst(reinterpret_cast<V *>(dp) + uint32_t(k), a);
+            gst(reinterpret_cast<V *>(dp) + (cs + uint32_t(k)), b);
+            gst(reinterpret_cast<V *>(dp) + (2 * cs + uint32_t(k)), c);
         }
     }
     return nv * n;
@@ -349,19 +352,19 @@ __device__ __forceinline__ bool fold_writeback_once(const KArgs &ka, const LT &L
         const u32 a = L.qbm[k], b = L.qm[k], c = L.qm1[k];
         low |= mfe16_inexact(sv(a)) || mfe16_inexact(sv(b)) || mfe16_inexact(sv(c));
         if (dp) {
-            dp[k] = a;
-            dp[Cs + k] = b;
-            dp[2 * Cs + k] = c;
+            gst(dp + uint32_t(k), a);
+            gst(dp + (uint32_t(Cs) + uint32_t(k)), b);
+            gst(dp + (2 * uint32_t(Cs) + uint32_t(k)), c);
         }
     }
     for (int k = tid; k <= N; k += NT) {
         const u32 q = L.q5[k];
         low |= mfe16_inexact(sv(q));
-        if (dp) dp[3 * Cs + k] = q;
+        if (dp) gst(dp + (3 * uint32_t(Cs) + uint32_t(k)), q);
     }
     if (dp) {
         const int C16 = (C + 15) >> 4;
-        for (int k = tid; k < C16; k += NT) inc.cc_dst[k] = reinterpret_cast<const uint4 *>(L.cc)[k];
+        for (int k = tid; k < C16; k += NT) gst(inc.cc_dst + uint32_t(k), reinterpret_cast<const uint4 *>(L.cc)[k]);
     }
     return low;
 }
@@ -405,11 +408,11 @@ __device__ __forceinline__ void fold_result(const KArgs &ka, int w, const int *v
     const int hv[2] = {q.x, q.y};
     for (int h = 0; h < 2; h++) {
         const double e = hv[h] >= 0x4000 ? double(INFINITY) : static_cast<double>(hv[h]) / 100.0;
-        gout[size_t(w) * ka.n_variants + vs[h]] = static_cast<float>(e);
+        gst(gout + size_t(w) * ka.n_variants + vs[h], static_cast<float>(e));
     }
     if (bad && ka.ovf) {
-        ka.ovf[w] = 1;
-        if (ka.tab) ka.tab_valid[w] = 0;
+        gst(ka.ovf + w, 1);
+        if (ka.tab) gst(ka.tab_valid + w, 0);
     }
 }
 

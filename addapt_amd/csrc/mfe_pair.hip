@@ -175,6 +175,12 @@ struct PLay {
 };
 static_assert(MFE_E4_SLOTS <= MFE_E4_MAX, "CP::e4 holds the generated slots");
 
+// variant v's words (global loads: fold_common.hpp gld)
+__device__ __forceinline__ DevVariant variant_at(const KArgs &ka, int v) {
+    const DevVariant *p = ka.variants + v;
+    return DevVariant{gld(&p->N), gld(&p->before_len), gld(&p->ctx), gld(&p->cons_off), gld(&p->motif), 0};
+}
+
 __device__ __forceinline__ int sext_lo(u32 x) { return int(short(x & 0xFFFFu)); }
 __device__ __forceinline__ int sext_hi(u32 x) { return int(x) >> 16; }
 __device__ __forceinline__ u32 pack2(int lo, int hi) { return (u32(lo) & 0xFFFFu) | (u32(hi) << 16); }
@@ -271,16 +277,16 @@ __device__ __forceinline__ void pair_constants(const DevScaled *__restrict__ XS,
     constexpr int NCT = (CT_SIZE + NT - 1) / NT;
     u32 v_ct[NCT];
 #pragma unroll
-    for (int t = 0; t < NCT; t++) v_ct[t] = gct[min(tid + t * NT, CT_SIZE - 1)];
+    for (int t = 0; t < NCT; t++) v_ct[t] = gld(gct + uint32_t(min(tid + t * NT, CT_SIZE - 1)));
     const DevTables &T0 = *TT;
-    const u32 v_mh = __float_as_uint((&T0.mmH[0][0][0])[min(tid, 199)]);
-    const u32 v_mi = __float_as_uint((&T0.mmI[0][0][0])[min(tid, 199)]);
-    const u32 v_ms = __float_as_uint((&T0.mlstem[0][0][0])[min(tid, 199)]);
-    const u32 v_ex = __float_as_uint((&T0.ext[0][0][0])[min(tid, 287)]);
-    const u32 v_tau = __float_as_uint(T0.termAU[tid & 7]);
+    const u32 v_mh = __float_as_uint(gld(&T0.mmH[0][0][0] + uint32_t(min(tid, 199))));
+    const u32 v_mi = __float_as_uint(gld(&T0.mmI[0][0][0] + uint32_t(min(tid, 199))));
+    const u32 v_ms = __float_as_uint(gld(&T0.mlstem[0][0][0] + uint32_t(min(tid, 199))));
+    const u32 v_ex = __float_as_uint(gld(&T0.ext[0][0][0] + uint32_t(min(tid, 287))));
+    const u32 v_tau = __float_as_uint(gld(T0.termAU + uint32_t(tid & 7)));
     const int ke = min(tid, MFE_E4_SLOTS * 4 - 1);
     const int e4a = MFE_E4_A[ke >> 2][ke & 3], e4u = MFE_E4_U[ke >> 2];
-    const u32 v_e4 = XS->ku16[e4u][max(e4a, 0)];
+    const u32 v_e4 = gld(&XS->ku16[e4u][max(e4a, 0)]);
 #pragma unroll
     for (int t = 0; t < NCT; t++)
         if (tid + t * NT < CT_SIZE) L.ct[tid + t * NT] = v_ct[t];
@@ -310,9 +316,9 @@ __device__ __forceinline__ bool pair_setup(const KArgs &ka, const DevScaled *__r
                                            unsigned long long *sst) {
     static_assert(NT == NWV * WAVE, "one wave per block slot");
     // (uni(): the kernel's loop makes every load from global memory a vector load)
-    DevVariant V = ka.variants[vs[0]];
+    DevVariant V = variant_at(ka, vs[0]);
     V.ctx = uni(V.ctx), V.cons_off = uni(V.cons_off);
-    const bool mh0 = uni(V.motif) != 0, mh1 = uni(ka.variants[vs[1]].motif) != 0;
+    const bool mh0 = uni(V.motif) != 0, mh1 = uni(gld(&ka.variants[vs[1]].motif)) != 0;
     const int N = uni(V.N);
     const int lane = tid & (WAVE - 1);
     const int wid = uni(tid / WAVE);
@@ -329,12 +335,12 @@ __device__ __forceinline__ bool pair_setup(const KArgs &ka, const DevScaled *__r
     // issued (the kernel prologue's loop per table waited on each load in turn, and the
     // setup tables' loads waited behind the restore's)
     static_assert(NT >= MAX_SPECIAL_HP && NT >= MAX_MOTIF && NT >= NM + 2, "one setup element per thread");
-    const u32 v_hp = __float_as_uint(XS->hp[min(tid, N)]);   // hairpin length factors (per-cell pass)
-    const int n_sp = uni(XS->n_special);
-    const uint32_t v_spk = XS->sp_key[min(tid, MAX_SPECIAL_HP - 1)];
-    const u32 v_spv = __float_as_uint(XS->sp_val[min(tid, MAX_SPECIAL_HP - 1)]);
-    const uint8_t v_mc = XS->motif_code[min(tid, MAX_MOTIF - 1)];
-    const int8_t v_mp = XS->motif_pt[min(tid, MAX_MOTIF - 1)];
+    const u32 v_hp = __float_as_uint(gld(XS->hp + uint32_t(min(tid, N))));   // hairpin length factors (per-cell pass)
+    const int n_sp = uni(gld(&XS->n_special));
+    const uint32_t v_spk = gld(XS->sp_key + uint32_t(min(tid, MAX_SPECIAL_HP - 1)));
+    const u32 v_spv = __float_as_uint(gld(XS->sp_val + uint32_t(min(tid, MAX_SPECIAL_HP - 1))));
+    const uint8_t v_mc = gld(XS->motif_code + uint32_t(min(tid, MAX_MOTIF - 1)));
+    const int8_t v_mp = gld(XS->motif_pt + uint32_t(min(tid, MAX_MOTIF - 1)));
     // position k = tid: its base (ViennaRNA's S1 wrap-around at 0 and N + 1) and constraints
     const uint8_t *cons = ka.cons + V.cons_off;
     const int np = N + 2;
@@ -344,18 +350,18 @@ __device__ __forceinline__ bool pair_setup(const KArgs &ka, const DevScaled *__r
         const uint8_t *bef = nullptr, *aft = nullptr;
         int blen = 0;
         if (V.ctx >= 0) {
-            bef = ka.ctx_seq + ka.ctx_off[4 * V.ctx + 0];
-            blen = ka.ctx_off[4 * V.ctx + 1];
-            aft = ka.ctx_seq + ka.ctx_off[4 * V.ctx + 2];
+            bef = ka.ctx_seq + gld(ka.ctx_off + 4 * V.ctx + 0);
+            blen = gld(ka.ctx_off + 4 * V.ctx + 1);
+            aft = ka.ctx_seq + gld(ka.ctx_off + 4 * V.ctx + 2);
         }
         const int pp = (kp == 0 ? N : (kp == N + 1 ? 1 : kp)) - 1;
         const uint8_t *sp = pp < blen ? bef + pp : (pp < blen + ka.Nraw ? raw + (pp - blen) : aft + (pp - blen - ka.Nraw));
-        v_sw = *sp;
-        v_up = cons[kp];
-        v_dn = cons[np + kp];
-        v_pt = cons[2 * np + kp];
-        v_en = cons[3 * np + kp];
-        v_fl = cons[4 * np + kp];
+        v_sw = gld(sp);
+        v_up = gld(cons + uint32_t(kp));
+        v_dn = gld(cons + uint32_t(np + kp));
+        v_pt = gld(cons + uint32_t(2 * np + kp));
+        v_en = gld(cons + uint32_t(3 * np + kp));
+        v_fl = gld(cons + uint32_t(4 * np + kp));
     }
     // ---- the stores: sequence, constraint arrays (mfe_cells.hip), tables
     if (tid < np) {
@@ -410,15 +416,15 @@ __device__ __forceinline__ bool pair_setup(const KArgs &ka, const DevScaled *__r
             // pair kk of the three tables' pairs: table kk / half, found by comparing (a
             // run-time division per load, and by zero at N <= 5, before)
             const size_t o = size_t(2 * kk) + (kk >= half ? gap : 0) + (kk >= 2 * half ? gap : 0);
-            rsv[t] = *reinterpret_cast<const uint2 *>(inc.src + o);
+            rsv[t] = gld(reinterpret_cast<const uint2 *>(inc.src + uint32_t(o)));
         }
 #pragma unroll
         for (int t = 0; t < RC; t++) {
             const int k = tid + t * NT;
-            rcv[t] = inc.cc_src[k < C16 ? k : 0];
+            rcv[t] = gld(inc.cc_src + uint32_t(k < C16 ? k : 0));
         }
-        rod = inc.src[min(tid, 2) * Cs + max(Crs - 1, 0)];
-        r5 = inc.src[3 * Cs + min(tid, N)];
+        rod = gld(inc.src + uint32_t(min(tid, 2) * Cs + max(Crs - 1, 0)));
+        r5 = gld(inc.src + uint32_t(3 * Cs + min(tid, N)));
     } else {
         const int C = ((N - 4) * (N - 3)) >> 1;
         for (int k = tid; k < C; k += NT) L.qm[k] = INF16;
@@ -427,7 +433,7 @@ __device__ __forceinline__ bool pair_setup(const KArgs &ka, const DevScaled *__r
     const unsigned long long st_s1 = __builtin_amdgcn_s_memtime();   // setup tables stored, restore issued
 #endif
     const bool constrained = block_or(L.flag, cst);
-    const int mL = uni(XS->motif_len);
+    const int mL = uni(gld(&XS->motif_len));
 #ifdef ADX_STAMP
     const unsigned long long st_s2 = __builtin_amdgcn_s_memtime();   // sequence, constraints
 #endif
@@ -501,7 +507,7 @@ __device__ __forceinline__ bool pair_setup(const KArgs &ka, const DevScaled *__r
     }
     tot = uni(tot);
     __syncthreads();
-    const u32 mx = u32(uni(int(__float_as_uint(XS->motif_extra))));
+    const u32 mx = u32(uni(int(__float_as_uint(gld(&XS->motif_extra)))));
     const u32 mextra = (mh0 ? (mx & 0xFFFFu) : 0x7FFFu) | (mh1 ? (mx & 0xFFFF0000u) : 0x7FFF0000u);
     if (tid == 0) q5_start(L, N);
 #ifdef ADX_STAMP
@@ -1011,17 +1017,14 @@ __device__ __forceinline__ void finalize(const CP &L, FRun &f, const BUni &U, in
 
 // log2 slices (lanes) per cell of a lane-set over P cells
 __device__ __forceinline__ int slices(int P) { return P <= 16 ? 2 : (P <= 32 ? 1 : 0); }
-// the record's two energies, each 16 bits wide, to packed apo | holo words
-__device__ __forceinline__ u32 lo2(u32 x) { return __builtin_amdgcn_perm(x, x, 0x05040504u); }
-__device__ __forceinline__ u32 hi2(u32 x) { return __builtin_amdgcn_perm(x, x, 0x07060706u); }
 
 // B: interior-loop partials (u >= 2) of diagonals d and d+1.
 // Lanes = the pairable cells of both (listed last step: ranks < P0 on d,
 // the rest on d+1); a lane of d+1 reads its inner cells at
 // off(d - 2 - u) + i + (N - d + 2 + u), which the blocks add per lane (hb).
-// cPP, cwd, cmm: load_list of this step; blk: the wave's block
+// cPP, cwd, cmm: load_list of this step; blk: the wave's block; E: the 1x1 .. 2x2 energies by code pair
 template <int blk>
-__device__ __forceinline__ void block_partials(const CP &L, const DevTables &T, BUni &U, int d, int lane, int sl, int cPP,
+__device__ __forceinline__ void block_partials(const CP &L, const uint16_t *E, BUni &U, int d, int lane, int sl, int cPP,
                                                u32 cwd, u32 cmm, bool constrained, u32 tauE, u32 fsm5 PSTAMP_PARAMS) {
     const int N = U.N, NP = L.np, NP2 = 2 * NP;
     const uint32_t ae4 = lds_addr(L.e4);
@@ -1064,7 +1067,7 @@ __device__ __forceinline__ void block_partials(const CP &L, const DevTables &T, 
                 auto has = [&](unsigned bits) { return ((bits >> (sh * 8 + blk)) & 1u) != 0; };
                 C.m23f = has(size_bits(5)) ? padd(L.ct[CT_M23O + oc], fsm5) : INF16;
                 C.t11 = C.t12 = C.t21 = C.t22 = INF16;
-                bcell_tables(C, L, T, N, dd, i, oc, uml, has(size_bits(2)), has(size_bits(3)), has(size_bits(4)));
+                bcell_tables(C, L, E, N, dd, i, oc, uml, has(size_bits(2)), has(size_bits(3)), has(size_bits(4)));
                 Acc a{INF16, INF16, INF16, INF16, INF16, INF16};
                 const bool mk = constrained && __ballot(C.A < uml || C.B < uml) != 0;
                 U.mk = mk;
@@ -1273,17 +1276,16 @@ __device__ __forceinline__ void mfe_pair_fold(const KArgs &ka, const DevScaled *
                                               const DevTables *__restrict__ TT, const int *vs, const CP &L,
                                               const IncM &inc, const bool constrained, const int lane,
                                               const unsigned long long *sst) {
-    const DevVariant V = ka.variants[vs[0]];
-    const int N = uni(V.N);
+    const int N = uni(gld(&ka.variants[vs[0]].N));
     constexpr int wid = WID;
     constexpr int fls = FW[0] == wid ? 0 : (FW[1] == wid ? 1 : -1);   // this wave's finalize lane-set
     const u32 *gct = reinterpret_cast<const u32 *>(XS->ctab);
     const Band bd = inc.band(N);
     // (uni(): vector loads inside the kernel's loop, scalar registers through the sweep)
-    const u32 mlclosing = u32(uni(int(__float_as_uint(XS->mlclosing))));
-    const u32 mlbase = u32(uni(int(__float_as_uint(XS->mlbase_sig))));
-    const u32 tauE = u32(uni(int(gct[CT_FSM + 6])));
-    const u32 fsm5 = u32(uni(int(gct[CT_FSM + 5])));
+    const u32 mlclosing = u32(uni(int(__float_as_uint(gld(&XS->mlclosing)))));
+    const u32 mlbase = u32(uni(int(__float_as_uint(gld(&XS->mlbase_sig)))));
+    const u32 tauE = u32(uni(int(gld(gct + CT_FSM + 6))));
+    const u32 fsm5 = u32(uni(int(gld(gct + CT_FSM + 5))));
     BUni U = buni(L, XS, N);
     U.fs1 = u32(uni(int(U.fs1)));
     if (wid == L_WAVE) {   // steps 0 (no B work: d + 1 < 8) and 1
@@ -1333,7 +1335,7 @@ __device__ __forceinline__ void mfe_pair_fold(const KArgs &ka, const DevScaled *
         PSTAMP(1);
         if constexpr (fls >= 0) finalize<NM, fls>(L, f, U, N, d, lane, mloF, mhiF, mlclosing, mlbase PSTAMP_ARGS);
         PSTAMP(2);
-        block_partials<wid>(L, *TT, U, d, lane, sl, cPP, cwd, cmm, constrained, tauE, fsm5 PSTAMP_ARGS);
+        block_partials<wid>(L, ka.loop16, U, d, lane, sl, cPP, cwd, cmm, constrained, tauE, fsm5 PSTAMP_ARGS);
         cPP = nPP, cwd = nwd, cmm = nmm;
         PSTAMP(3);
         if (wid == MW[0] || wid == MW[1]) split_rows(L, bd, wid == MW[0] ? d : d + 1, lane);
@@ -1430,23 +1432,39 @@ mfe_pair_kernel(const PairArgs args) {
         if (!uni(int(wr.on))) continue;   // without an order list: a walker the mask leaves out
         const int w = uni(wr.w), cur = uni(wr.cur), c0 = uni(wr.c0), c1 = uni(wr.c1);
         const bool valid = uni(int(wr.valid)) != 0;
-        const int vs[2] = {uni(ka.groups2[2 * g]), uni(ka.groups2[2 * g + 1])};
+        const int vs[2] = {uni(gld(ka.groups2 + 2 * g)), uni(gld(ka.groups2 + 2 * g + 1))};
+        // both in one word for the result (nothing in the sweep reads them; opaque, or the two
+        // stay live through it as they are): the launcher bounds n_variants
+        int vsp = vs[0] | (vs[1] << 16);
+        asm volatile("" : "+s"(vsp));
         IncM inc{nullptr, nullptr, 0, 0, nullptr, nullptr};
         if (ka.tab) {
             inc = inc_slots(ka, w, g, cur);
+            inc.dst = nullptr, inc.cc_dst = nullptr;   // (the write-back works them out)
             // a sibling group may clear tab_valid[w] on overflow while this one reads it:
             // either value is correct (an incremental refold equals a fold from scratch)
-            if (valid && c0 >= 0) inc_refold(inc, ka, w, g, cur, c0, c1, uni(ka.variants[vs[0]].before_len));
+            if (valid && c0 >= 0) inc_refold(inc, ka, w, g, cur, c0, c1, uni(gld(&ka.variants[vs[0]].before_len)));
         }
         unsigned long long sst[7] = {0, 0, 0, 0, 0, 0, 0};
+        // the folded length for the write-back, loaded here (one SGPR through the fold; the
+        // address of the word, kept for a load after the sweep, was a spilled pair)
+        const int N = uni(gld(&ka.variants[vs[0]].N));
         const bool constrained = pair_setup<NT, NM>(ka, XS, TT, vs, seqs + size_t(w) * ka.Nraw, L, inc, tid, sst);
         pair_fold_wave<NT, NM>(std::make_integer_sequence<int, NWV>{}, uni(tid / WAVE), ka, XS, TT, vs, L, inc,
                                constrained, tid & (WAVE - 1), sst);
         // the fold's write-back and 16-bit range check (one copy for all waves)
-        const int N = uni(ka.variants[vs[0]].N);
         const u32 z = L.q5[N];
+        if (ka.tab) {
+            // the slot the fold writes, worked out again from the walker's words (opaque, or the
+            // addresses of the pass's start stay live through the sweep: two spilled pairs)
+            int cw = cur;
+            asm volatile("" : "+s"(cw));
+            const IncM to = inc_slots(ka, w, g, cw);
+            inc.dst = to.dst, inc.cc_dst = to.cc_dst;
+        }
+        const int ve[2] = {vsp & 0xFFFF, int(uint32_t(vsp) >> 16)};
         const bool bad = block_or(L.flag + 1, fold_writeback_once<NT>(ka, L, inc, N, tid));   // (mfe_cells.hip: __syncthreads_or)
-        if (tid == 0) fold_result(ka, w, vs, gout, z, bad);
+        if (tid == 0) fold_result(ka, w, ve, gout, z, bad);
     }
 }
 
@@ -1455,7 +1473,7 @@ static hipError_t launch_pair_nm(const KArgs &ka, const uint8_t *seqs, int W, fl
                                  hipStream_t stream, int grid) {
     constexpr size_t lds = PLay<NM>::BYTES;
     auto k = mfe_pair_kernel<NWV * WAVE, NM>;
-    if (!ka.pairq) return hipErrorInvalidValue;
+    if (!ka.pairq || ka.n_variants > 0x10000) return hipErrorInvalidValue;   // (the kernel packs two variant indices in a word)
     // the carve addresses LDS from 0 (lds_at): no static LDS may precede the block
     hipError_t e = configure_dynamic_lds(k, lds, true);
     if (e != hipSuccess) return e;
@@ -1495,8 +1513,9 @@ static hipError_t launch_pair_nm(const KArgs &ka, const uint8_t *seqs, int W, fl
 
 }  // namespace
 
-// The pair kernel covers folded lengths up to 100 (two 100-nt walkers per CU).
-bool mfe_pair_covers(const KArgs &ka) { return ka.Nmax <= 100; }
+// The pair kernel covers folded lengths up to 100 (two 100-nt walkers per CU) and variant
+// indices of 16 bits (it carries a group's two in one word).
+bool mfe_pair_covers(const KArgs &ka) { return ka.Nmax <= 100 && ka.n_variants <= 0x10000; }
 
 hipError_t launch_mfe_pair(const KArgs &ka, const uint8_t *seqs, int W, float *gout, const int *mask,
                            hipStream_t stream, int grid) {

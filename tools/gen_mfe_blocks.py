@@ -287,10 +287,14 @@ def emit_table_decl(blk, out):
         out.append("    u32 tv_%s = INF16, ti_%s = 0u;" % (k, k))
 
 
-def emit_table_fin(blk, out):
+def emit_table_fin(blk, out, v):
+    """The pair kernel's C.t11 .. C.t22 hold 16 bits as loaded (mfe_common.hpp bcell_tables):
+    widened to both halves here, at the use, so that nothing waits for the load before."""
     out.append("fin:")
     for k in table_kinds(blk):
         tab = {"i11": "C.t11", "i12": "C.t12", "i21": "C.t21", "i22": "C.t22"}[k]
+        if v.pair:
+            tab = "lo2(%s)" % tab
         out.append("    a.s = pmin(a.s, padd(tv_%s, padd(ti_%s, %s)));" % (k, k, tab))
     out.append("    return;")
 
@@ -480,7 +484,7 @@ def emit_block_cells_sliced(v, blk, S, out):
     for u in blk:
         out.append("    if (um < %d) goto fin;" % u)
         emit_sliced_batch(v, [(u, "a")], S, out, "    ")
-    emit_table_fin(blk, out)
+    emit_table_fin(blk, out, v)
 
 
 def main():
@@ -524,7 +528,7 @@ def emit_file(v):
             emit_group_asm(u, out)
             out.append("    }")
             out.append("    MFE_SCHED_BARRIER();   // bound the scheduling window (VGPR / SGPR pressure)")
-        emit_table_fin(blk, out)
+        emit_table_fin(blk, out, v)
         out.append("}")
         out.append("")
     out.append("__device__ __forceinline__ void mfe_block(int b, const BUni &U, const BCell &C, Acc &a) {")
