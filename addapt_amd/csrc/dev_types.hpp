@@ -79,7 +79,7 @@ struct DevScaled {
     // MFE only (mfe_cells.hip): generic interior energy = il[u] + nin[|n1 - n2|]
     float il[32];            // interior[u]
     float nin[32];           // min(MAX_NINIO, k * ninio)
-    // MFE packed (upload_mfe16) only, per loop size u: il[u] + nin[k] (k = 0..5),
+    // MFE packed (pack_mfe16) only, per loop size u: il[u] + nin[k] (k = 0..5),
     // bulge[u], 1 x (u-1) -- the interior-loop blocks' uniform energy record
     uint32_t ku16[32][8];
     // interior term lists (see NS_MAX); *_cnt[umax] = terms with u <= umax
@@ -169,7 +169,7 @@ struct KArgs {
     const int *bvars;           // [n_bvars] variants folded with an outside pass
     int n_bvars;
     const int *bvar_slot;       // [n_bvars] the variant's tables in the groups2 slot layout
-                                //   (2 * group + half; host-computed, adx_api.cpp upload_all)
+                                //   (2 * group + half; host-computed, setup_core.hpp outside_slots)
     const int *pairs;           // [n_pairs][3]: bvars index, i, j (1-based, folded coordinates)
     int n_pairs;
     const double *pair_p;       // [W][n_pairs] probabilities written by bppm_kernel (score input)

@@ -79,7 +79,7 @@ static KArgs packed16(const KArgs &ka) {   // the packed 16-bit MFE kernels' ene
 }
 
 // PF folds longer than pf_cells covers take the ring kernel (pf_ring.hip).
-// One choice per context (adx_api.cpp upload_all): it fixes the layout of the
+// One choice per context (api_problem.hpp upload_all): it fixes the layout of the
 // walkers' stored tables, which every later kernel of the context must read
 // the same way.
 bool pf_ring_layout(const KArgs &ka) {

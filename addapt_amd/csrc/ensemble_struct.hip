@@ -1,5 +1,5 @@
 // gfx950 centroid and maximum-expected-accuracy (MEA) structures from pair
-// probabilities (RNAfold -p --MEA): an off-step utility (adx_api.cpp
+// probabilities (RNAfold -p --MEA): an off-step utility (the C ABI's
 // adx_*ensemble_structures*), not the Monte Carlo score.  ensemble_struct_kernel
 // reads the matrices launch_bppm left on the device, one workgroup of 256
 // threads per sequence, and returns two strings and three doubles for each.

@@ -1,5 +1,5 @@
 // Host interface of the engine's translation units: every function that
-// crosses a file is declared here, once.  Each .hip file and adx_api.cpp
+// crosses a file is declared here, once.  Each .hip file and the C ABI (api_*)
 // include it; none declares another file's function by hand.
 #pragma once
 

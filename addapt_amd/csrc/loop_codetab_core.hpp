@@ -1,5 +1,5 @@
 // The 1x1, 1x2, 2x1 and 2x2 interior-loop energies of the packed 16-bit MFE
-// tables by code pair (mfe_pair.hip bcell_tables; built at upload, adx_api.cpp).
+// tables by code pair (mfe_pair.hip bcell_tables; built at upload, api_problem.hpp).
 //
 // A B cell holds two byte codes: the closing pair's oc = type * 25 + S[i+1] * 5
 // + S[j-1] and the inner pair's code c = rtype * 25 + S[q+1] * 5 + S[p-1] (CP::cc,

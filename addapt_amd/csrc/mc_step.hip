@@ -420,7 +420,7 @@ __device__ __forceinline__ int fold_class(const StepArgs &st, const Proposed &p,
 // proposed sequences and its MT streams' next words are loaded in one batch
 // first; the sequence the proposal starts from is staged in LDS.
 constexpr int TAIL_NMAX = 256;   // sequences staged whole
-static_assert(NMAX < TAIL_NMAX, "adx_api limits sequences to NMAX: the step tail stages them whole");
+static_assert(NMAX < TAIL_NMAX, "the C ABI limits sequences to NMAX: the step tail stages them whole");
 constexpr int TAIL_WPB = 4;      // walkers (waves) per workgroup
 __global__ void __launch_bounds__(TAIL_WPB * 64) step_tail_kernel(StepArgs st, KArgs kc, int comb, double *tv,
                                                                   int s_acc, long long step, int s_prop, int nt_tot) {
@@ -580,7 +580,7 @@ static hipError_t launch_window(const KArgs &ka, const StepArgs &st, const int *
 
 // evs (optional): 4 * nsteps events per step: window start, outside pass
 // start, outside pass end, window end (score written); the inside share of a
-// window is the window minus its outside pass (adx_api.cpp).  Launches:
+// window is the window minus its outside pass (api_ctx.cpp).  Launches:
 // step_tail_kernel (the first proposals), then per step the score window and
 // step_tail_kernel (its decisions and the next step's proposals).
 hipError_t launch_steps(const KArgs &ka, const StepArgs &st0, hipStream_t stream, hipEvent_t *evs) {

@@ -1,6 +1,6 @@
 // gfx950 minimum-free-energy fold WITH the structure: mfe_trace_kernel fills
 // the Zuker tables of one (sequence, variant) per workgroup and traces the
-// optimal structure back on the device.  An off-step utility (adx_api.cpp
+// optimal structure back on the device.  An off-step utility (the C ABI's
 // adx_*mfe_structure*), not the Monte Carlo score: same recursion and energy
 // tables as the score's MFE kernels (oracle/fold.c orc_mfe_energy), written
 // for clarity, with no 16-bit range and no fallback.

@@ -28,7 +28,7 @@
 //   P(i,j)    = qb(i,j) qbb(i,j) / Z
 //
 // Covered: unconstrained folds (the pair terms' folds are the conditions'
-// unconstrained folds, adx_api.cpp), N <= 112 (LDS); everything else takes
+// unconstrained folds, api_ctx.cpp), N <= 112 (LDS); everything else takes
 // fold_rows.hip bppm_kernel.
 //
 // What it shares with outside_ring.hip is in outside_common.hpp; here: the

@@ -396,7 +396,7 @@ __device__ __forceinline__ void b_sweep(const OxL &L, int N, int lane, Wid wid, 
 // The sequence with its contexts (fold_rows.hip pf_group; ViennaRNA S1 wrap),
 // the ct / dt tables, the constant factor of each shape (u, n1) -- generic
 // fgen, bulge / 1xn length factors, the sigma powers of the tabulated loops
-// (adx_api.cpp addS) -- q5 from the slot (q5g) and the zeroed rings, site
+// (setup_core.hpp addS) -- q5 from the slot (q5g) and the zeroed rings, site
 // weights and pair values.  Every thread of the workgroup calls it (barriers)
 __device__ __forceinline__ void ox_setup(const OxL &L, const KArgs &ka, const DevScaled *XS, const DevVariant &V,
                                          const uint8_t *seqs, int w, const float *q5g, int N, int tid) {

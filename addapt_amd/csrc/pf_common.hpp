@@ -128,7 +128,7 @@ __device__ __forceinline__ PfL<typename K::V> pf_carve(char *smem, const Lay &Y,
 }
 
 // ---------------------------------------------------------------- interior-loop shapes
-// constant factor of shape (u, n1) (adx_api.cpp addS / fgen)
+// constant factor of shape (u, n1) (setup_core.hpp addS / fgen)
 __device__ __forceinline__ float shape_factor(const DevScaled *XS, int u, int n1) {
     const int kd = loop_kind(n1, u - n1);
     const float *p = kd < 0 ? XS->fgen + (u - 6) * FG_ROW + n1 - 2
@@ -194,7 +194,7 @@ __device__ __forceinline__ void pshape_seq(std::integer_sequence<int, N1s...>, c
     (pshape1<U, N1s, MK>(L, c, fv, qb, cc, bits, g, sp), ...);
 }
 // A size <= 5 (the stack, 1x1..2x3 table loops), every shape by one lane.  Every
-// shape factor is symmetric in (n1, n2) (adx_api.cpp build_scaled): a size keeps
+// shape factor is symmetric in (n1, n2) (setup_core.hpp build_scaled): a size keeps
 // U/2 + 1 of them, shape n1 reads fv[min(n1, U - n1)]
 template <class K, int U>
 struct PSize {

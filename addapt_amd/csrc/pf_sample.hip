@@ -1,5 +1,5 @@
 // gfx950 structures drawn from the Boltzmann ensemble (vrna_pbacktrack): an
-// off-step utility (adx_api.cpp adx_*sample_structures*), not the Monte Carlo
+// off-step utility (the C ABI's adx_*sample_structures*), not the Monte Carlo
 // score.  Two kernels, so that many workgroups can sample from one sequence's
 // tables:
 //

@@ -4,7 +4,7 @@ The fold kernels apply the unpaired-run limits of interior loops only when
 their setup found the fold constrained, and that test reads the positions'
 flags and enforced partners.  A '|' once set neither, only up[i] = 0 (the base
 may not stay unpaired), so a '|'-only constraint folded with interior loops
-closed over the marked base; it has a flag bit of its own now (adx_api.cpp
+closed over the marked base; it has a flag bit of its own now (setup_core.hpp
 build_constraint).  Each fold kernel's energies are compared with the oracle's here
 (pf_cells / pf_ring / mfe_pair / mfe_cells through score_batch; the rows kernel
 and bppm_kernel through test_gpu_bppm.py's constrained matrices).

@@ -130,7 +130,7 @@ def _anchor(oracle, L, target):
     """(template, its ensemble energy): a G.C helix in poly-A of L nt whose ensemble
     energy is the nearest to target kcal/mol.  A PF context scales its FP32 tables
     by exp(g0 / kT) per nucleotide, g0 = min(-0.05, the template's ensemble energy
-    / L) (adx_api.cpp calibrate)."""
+    / L) (api_problem.hpp calibrate)."""
     if L not in _anchors:
         helices = ["G" * k + "AAAA" + "C" * k + "A" * (L - 2 * k - 4) for k in range(0, 31)]
         _anchors[L] = [(oracle.pf_energy(s), s) for s in helices]

@@ -176,7 +176,7 @@ def test_ring_trajectory_short_variants(native, oracle):
 def _longest_context(native):
     """The longest synthetic template a context accepts (the ring kernels take
     up to RG_NMAX = 190 nt; the context also sizes the stateless score
-    kernel's LDS layout, adx_api.cpp choose_layout, which ends lower)."""
+    kernel's LDS layout, api_problem.hpp check_lds, which ends lower)."""
     terms = workloads.default_objective()
     apt = (workloads.THEO_SEQ, workloads.THEO_FOLD, native.theo_energy())
     for N in range(190, 149, -1):

@@ -8,7 +8,7 @@ vrna_exp_E_ml_fast unpaired-prefix term) not as the sum
 
 but as U(i, j) = qm1(i, j) + [up_i >= 1] pw U(i + 1, j), which holds because
 the hard-constraint arrays give up_i = up_{i+1} + 1 whenever up_i >= 1
-(adx_api.cpp, the unpaired-run lengths).  This checks the identity in float64
+(setup_core.hpp, the unpaired-run lengths).  This checks the identity in float64
 on random constraint masks and tables (CPU, no GPU)."""
 import numpy as np
 import pytest
