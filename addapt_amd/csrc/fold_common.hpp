@@ -1,6 +1,11 @@
-// Helpers shared by the fold kernels (fold_rows.hip, mfe_cells.hip, ...): cell
-// indexing of the DP tables, pair types, the LDS-only barrier, the packed
-// 16-bit min-plus encoding and the per-cell table block layout.
+// Helpers shared by the fold kernels (fold_rows.hip, mfe_cells.hip, ...) that
+// need HIP: global-address-space loads and stores, the LDS-only barrier and the
+// workgroup OR, a fold workgroup's walker words, the packed 16-bit min-plus
+// range, the special-hairpin lookup, a refold's band, the motif sites by wave
+// (motif_scan, motif_constraints) and the quad sum over four DPP lanes.  The
+// pure index arithmetic -- cell indexing, pair types, loop kinds, allowed(), the
+// folded sequence in its context, the scalar motif site, the per-cell table
+// block layout -- is fold_setup_core.hpp, included here for every kernel.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -8,6 +13,9 @@
 #include <cstdint>
 
 #include "dev_types.hpp"
+
+#define FS_FN __device__ __forceinline__
+#include "fold_setup_core.hpp"
 
 // Diagnostic builds (-DADX_STAMP) only, never the product: add the cycles
 // (s_memtime) since the wave's last stamp to its phase counter k.  st_acc and
@@ -30,9 +38,6 @@ namespace adx {
 namespace {
 
 constexpr int WAVE = 64;
-
-// index of the first cell of diagonal dd (cells with j - i = dd >= 4)
-__device__ __forceinline__ int off(int dd, int N) { return ((dd - 4) * (2 * N - 3 - dd)) >> 1; }
 
 __device__ __forceinline__ int uni(int x) { return __builtin_amdgcn_readfirstlane(x); }
 
@@ -163,23 +168,6 @@ __device__ __forceinline__ int special_hp(const uint32_t *spk, uint32_t key) {
     return hit;
 }
 
-// ---------------------------------------------------------------- hard constraints
-// flg bits: 1 = 'x' (no pair), 2 = '<' (pairs upstream), 4 = '>' (downstream),
-// 8 = '|' (pairs; allowed() does not read it, but the kernels' setup takes any
-// flag or partner as "this fold is constrained", and a '|' sets nothing else);
-// ptn = enforced partner (0 none); enc = innermost enclosing enforced pair id.
-// L: any LDS carve with the byte arrays flg, ptn, enc.
-template <class LT>
-__device__ __forceinline__ bool allowed(const LT &L, int i, int j) {
-    const int fi = L.flg[i], fj = L.flg[j];
-    if ((fi | fj) & 1) return false;
-    if ((fi & 2) || (fj & 4)) return false;
-    const int pi = L.ptn[i], pj = L.ptn[j];
-    if (pi) return pi == j;
-    if (pj) return pj == i;
-    return L.enc[i] == L.enc[j];
-}
-
 // The band of a refold after positions m_lo .. m_hi changed: rows clo .. chi of
 // span dd hold the cells of qbm / qm1 that contain a changed position (or the
 // neighbour whose dangle they read), rows qlo .. qhi of span s the cells of qm
@@ -193,54 +181,84 @@ struct Band {
     __device__ __forceinline__ int qhi(int s) const { return incr ? min(N - s, m_hi + 2) : N - s; }
 };
 
-// interior-loop shape kinds (dev_types.hpp TermKind; -1 = generic)
-__host__ __device__ constexpr int loop_kind(int n1, int n2) {
-    return (n1 == 0 && n2 == 0) ? TK_STK
-         : (n1 + n2 == 1) ? TK_B1
-         : (n1 == 0 || n2 == 0) ? TK_BUL
-         : (n1 == 1 && n2 == 1) ? TK_I11
-         : (n1 == 1 && n2 == 2) ? TK_I12
-         : (n1 == 2 && n2 == 1) ? TK_I21
-         : (n1 == 2 && n2 == 2) ? TK_I22
-         : ((n1 == 2 && n2 == 3) || (n1 == 3 && n2 == 2)) ? TK_M23
-         : (n1 == 1 || n2 == 1) ? TK_1N
-         : -1;
+// ---------------------------------------------------------------- motif sites by wave
+// The sequence scan, one lane per start o: mat[o] = the motif's bases stand at o
+template <int NT, class LT>
+__device__ __forceinline__ void motif_scan(const LT &L, const uint8_t *mcode, int mL, int N, int tid) {
+    for (int o = tid + 1; o + mL - 1 <= N; o += NT) L.mat[o] = motif_seq_match(L.S, mcode, mL, o) ? 1 : 0;
+}
+// The constraints, after a barrier: one of the NW waves per matching start o,
+// lanes = motif positions with partner table mpt (fold_setup_core.hpp
+// motif_site's second half, spread over the lanes)
+template <int NW, class LT>
+__device__ __forceinline__ void motif_constraints(const LT &L, const int8_t *mpt, int mL, int N, int wid, int lane) {
+    for (int o = 1 + wid; o + mL - 1 <= N; o += NW) {
+        if (!uni(L.mat[o])) continue;
+        bool ok = true;
+        for (int k = lane; k < mL; k += WAVE) {
+            const int pk = mpt[k];
+            if (pk < 0) ok = ok && L.up[o + k] >= 1;
+            else if (pk > k) ok = ok && allowed(L, o + k, o + pk);
+        }
+        const bool all = __ballot(!ok) == 0;
+        if (lane == 0) L.mat[o] = all ? 1 : 0;
+    }
 }
 
-// Pair type / reversed type / terminal-AU flag without a memory lookup:
-// PAIR[a][b] for codes a, b in 0..4 (ViennaRNA types 1..6) packed 3 bits per
-// entry of index 5a+b-9 (the canonical pairs sit at 9..23).
-constexpr unsigned long long pack_pairs() {
-    unsigned long long k = 0;
-    k |= 5ull << (3 * (9 - 9));    // A-U
-    k |= 1ull << (3 * (13 - 9));   // C-G
-    k |= 2ull << (3 * (17 - 9));   // G-C
-    k |= 3ull << (3 * (19 - 9));   // G-U
-    k |= 6ull << (3 * (21 - 9));   // U-A
-    k |= 4ull << (3 * (23 - 9));   // U-G
-    return k;
+// ---------------------------------------------------------------- the structure kernels' setup
+// mfe_trace.hip and pf_sample.hip, NT threads: the sequence in its context, the
+// variant's constraint arrays, the special hairpins (values through
+// special_value(listed, table value)), the motif tables, the wrap and the motif
+// sites into L (TraceLds, PfSeqLds: the same field names); ends with a barrier
+template <int NT, class LT, class SV>
+__device__ void seq_setup(LT &L, const KArgs &ka, const DevVariant &V, const uint8_t *raw, int tid, SV special_value) {
+    const DevScaled *X = ka.X;
+    const int N = V.N, np = N + 2;
+    const uint8_t *cons = ka.cons + V.cons_off;
+    const SeqSrc src = seq_src(ka, V, raw);
+    for (int k = tid; k < np; k += NT) {
+        L.S[k] = src.code(k, N);
+        L.up[k] = cons[k];
+        L.ptn[k] = cons[2 * np + k];
+        L.enc[k] = cons[3 * np + k];
+        L.flg[k] = cons[4 * np + k];
+        L.mat[k] = 0;
+    }
+    for (int k = tid; k < MAX_SPECIAL_HP; k += NT) {
+        const bool on = k < X->n_special;
+        L.spk[k] = on ? X->sp_key[k] : 0xFFFFFFFFu;   // hp_key never sets the top bits
+        L.spv[k] = special_value(on, X->sp_val[k]);
+    }
+    for (int k = tid; k < MAX_MOTIF; k += NT) {
+        L.mcode[k] = X->motif_code[k];
+        L.mpt[k] = X->motif_pt[k];
+    }
+    __syncthreads();
+    if (tid == 0) wrap_ends(L, N);   // (no motif site reads the two ends)
+    const int mL = X->motif_len;
+    if (V.motif != 0 && mL > 0)
+        for (int o = tid + 1; o + mL - 1 <= N; o += NT) L.mat[o] = motif_site(L, L.mcode, L.mpt, mL, o) ? 1 : 0;
+    __syncthreads();
 }
-__device__ __forceinline__ int ptype(int a, int b) {
-    const int idx = 5 * a + b - 9;
-    return (idx >= 0 && idx <= 14) ? int((pack_pairs() >> (3 * idx)) & 7ull) : 0;
+
+// ---------------------------------------------------------------- quad sum
+typedef float f2 __attribute__((ext_vector_type(2)));
+// v + (v of the lane DPP control CTRL selects; 0 where it selects none)
+template <int CTRL>
+__device__ __forceinline__ float dpp_add(float v) {
+    return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false));
 }
-__device__ __forceinline__ int rtype(int t) { return t ? (((t - 1) ^ 1) + 1) : 0; }
-
-// Cell indexing (1-based i < j, span j - i >= 4):
-//   qbm, cc  diagonal-major  off(j-i) + i - 1   (cells of one anti-diagonal contiguous)
-//   qm       row-major       rowb(i) + j - i - 4 (qm[i][*] contiguous)
-//   qm1      column-major    colb(j) + i - 1     (qm1[*][j] contiguous)
-// so every inner loop of the recurrence walks contiguous LDS at a per-lane base.
-__device__ __forceinline__ int rowb(int i, int N) { return (i - 1) * (N - 3) - (((i - 1) * i) >> 1); }
-__device__ __forceinline__ int colb(int j) { return ((j - 5) * (j - 4)) >> 1; }
-
-// LDS per-cell table block (L.dt), copied from DevTables / DevScaled
-constexpr int DT_MMH = 0;      // [type][x][y] hairpin mismatch
-constexpr int DT_MMI = 200;    // [type][x][y] interior mismatch
-constexpr int DT_MLS = 400;    // [type][x][y] multiloop stem
-constexpr int DT_EXT = 600;    // [type][6][6] exterior stem
-constexpr int DT_TAU = 888;    // [type] terminal AU
-constexpr int DT_HP = 896;     // [u] hairpin length factor
+template <int CTRL>
+__device__ __forceinline__ f2 dpp_add(f2 v) {
+    const float x = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v.x), CTRL, 0xf, 0xf, false));
+    const float y = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v.y), CTRL, 0xf, 0xf, false));
+    return v + f2{x, y};
+}
+template <class V>
+__device__ __forceinline__ V quad_sum(V v) {   // sum over the 4 lanes of a quad, in every lane
+    v = dpp_add<0xb1>(v);      // quad_perm [1,0,3,2]
+    return dpp_add<0x4e>(v);   // quad_perm [2,3,0,1]
+}
 
 }  // namespace
 }  // namespace adx

@@ -557,23 +557,10 @@ __device__ void pf_group(const KArgs &ka, const int *vs, const uint8_t *raw, con
     // ---- per-group setup: sequence, constraint arrays, motif sites
     const uint8_t *cons = ka.cons + V.cons_off;
     const int np = N + 2;
-    const uint8_t *bef = nullptr, *aft = nullptr;
-    int blen = 0;
-    if (V.ctx >= 0) {
-        bef = ka.ctx_seq + ka.ctx_off[4 * V.ctx + 0];
-        blen = ka.ctx_off[4 * V.ctx + 1];
-        aft = ka.ctx_seq + ka.ctx_off[4 * V.ctx + 2];
-    }
+    const SeqSrc src = seq_src(ka, V, raw);
     bool constrained = false;
     for (int k = tid; k < np; k += NT) {
-        uint8_t s = 0;
-        if (k >= 1 && k <= N) {
-            const int pp = k - 1;
-            if (pp < blen) s = bef[pp];
-            else if (pp < blen + ka.Nraw) s = raw[pp - blen];
-            else s = aft[pp - blen - ka.Nraw];
-        }
-        L.S[k] = s;
+        L.S[k] = src.code(k, N);
         const uint8_t f = cons[4 * np + k], pt = cons[2 * np + k];
         L.up[k] = cons[k];
         L.dn[k] = cons[np + k];
@@ -591,29 +578,14 @@ __device__ void pf_group(const KArgs &ka, const int *vs, const uint8_t *raw, con
         for (int k = tid; k < C; k += NT) L.qm[0][k] = SR::zero();
     }
     constrained = __syncthreads_or(constrained);
-    if (tid == 0) {
-        // ViennaRNA's S1 wrap-around (only reaches values that are never used)
-        L.S[0] = L.S[N];
-        L.S[N + 1] = L.S[1];
-    }
+    if (tid == 0) wrap_ends(L, N);   // (only reaches values that are never used)
     bool any_motif = false;
 #pragma unroll
     for (int p = 0; p < P; p++) any_motif |= motif[p];
     const int mL = XS->motif_len;
-    if (any_motif && mL > 0) {
-        for (int o = tid + 1; o + mL - 1 <= N; o += NT) {
-            bool ok = true;
-            for (int k = 0; k < mL && ok; k++) {
-                if (L.S[o + k] != XS->motif_code[k]) ok = false;
-            }
-            for (int k = 0; k < mL && ok; k++) {
-                const int pk = XS->motif_pt[k];
-                if (pk < 0) ok = L.up[o + k] >= 1;
-                else if (pk > k) ok = allowed(L, o + k, o + pk);
-            }
-            L.mat[o] = ok ? 1 : 0;
-        }
-    }
+    if (any_motif && mL > 0)
+        for (int o = tid + 1; o + mL - 1 <= N; o += NT)
+            L.mat[o] = motif_site(L, XS->motif_code, XS->motif_pt, mL, o) ? 1 : 0;
     __syncthreads();
     const float sig1 = XS->sig[1];
     const float mlbase_sig = XS->mlbase_sig;
@@ -659,6 +631,7 @@ __device__ void pf_group(const KArgs &ka, const int *vs, const uint8_t *raw, con
                                 if (XS->sp_key[k] == key) { h = XS->sp_val[k]; special = true; break; }
                         }
                         if (!special)
+                            // (hairpin_dt_index, open-coded as in mfe_cells.hip: a select between two loads)
                             h = SR::mul(L.dt[DT_HP + u],
                                         (u == 3) ? L.dt[DT_TAU + type]
                                                  : L.dt[DT_MMH + type * 25 + L.S[i + 1] * 5 + L.S[j - 1]]);

@@ -290,7 +290,7 @@ struct Proposed {
 // acc took it); acc's score difference is the auto thermostat's training
 // value.  a, c: the streams, their next words staged by the tail (MtView).
 __device__ Proposed propose_walker(const StepArgs &st, long long step, int s, int w, int lane, const Accepted &acc,
-                                   const TailIn &in, const uint8_t *seq, MtView &a, MtView &c, bool end_cells) {
+                                   const TailIn &in, const uint8_t *seq, MtView &a, MtView &c) {
     Proposed out;
     if (in.err) {
         if (lane == 0) st.changed[w] = 0;
@@ -356,9 +356,11 @@ __device__ Proposed propose_walker(const StepArgs &st, long long step, int s, in
     // The end cells read a wrapped dangle: cells (i, N) the base S[N + 1] = S[1],
     // cells (1, j) the base S[0] = S[N].  No fold uses their qm1 values, so the band
     // of a refold (fold_common.hpp Band) leaves them out; the outside pass on the
-    // stored tables reads them and divides by the proposal's mismatch factor.  With
-    // pair terms (end_cells) a proposal that changes an end base folds from scratch
-    if (changed && end_cells && (plo == 0 || phi == st.Nraw - 1)) plo = phi = -1;
+    // stored tables reads them and divides by the proposal's mismatch factor, and so
+    // do the exterior sums of the kernels that recompute every cell's code but restore
+    // qbm outside the band (mfe_cells.hip, fold_rows.hip: the restored value carries
+    // the old code's mismatch).  A proposal that changes an end base folds from scratch
+    if (changed && (plo == 0 || phi == st.Nraw - 1)) plo = phi = -1;
     double u = 0.0;
     if (e == 0 && changed) u = mt_canonical(c, lane);
     if (a.twisted)
@@ -490,7 +492,7 @@ __global__ void __launch_bounds__(TAIL_WPB * 64) step_tail_kernel(StepArgs st, K
     wave_sync();
     MtView a{mt, gA, in.ia, in.ia, min(in.ia + 8, 624), false};
     MtView c{mt + MT_WORDS, gC, in.ic, in.ic, min(in.ic + 8, 624), false};
-    const Proposed p = propose_walker(st, step, s_prop, w, lane, acc, in, seq, a, c, kc.n_pairs > 0 && kc.mode == 0);
+    const Proposed p = propose_walker(st, step, s_prop, w, lane, acc, in, seq, a, c);
     if (lane == 0) {
         if (st.ovf) st.ovf[w] = 0;   // set again by this proposal's fold if it leaves the 16-bit range
         if (st.cls) st.cls[w] = uint8_t(fold_class(st, p, acc.tab_valid >= 0 ? acc.tab_valid : in.tabv));

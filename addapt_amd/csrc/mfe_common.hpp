@@ -271,22 +271,6 @@ __device__ __forceinline__ void inc_refold(IncM &inc, const KArgs &ka, int w, in
 }
 
 // ---------------------------------------------------------------- setup and finish pieces
-// The motif sites' constraints: one wave per matching start o (mat[o] set by the
-// sequence scan), lanes = motif positions with partner table mpt
-template <class LT>
-__device__ __forceinline__ void motif_constraints(const LT &L, const int8_t *mpt, int mL, int N, int wid, int lane) {
-    for (int o = 1 + wid; o + mL - 1 <= N; o += NWV) {
-        if (!uni(L.mat[o])) continue;
-        bool ok = true;
-        for (int k = lane; k < mL; k += WAVE) {
-            const int pk = mpt[k];
-            if (pk < 0) ok = ok && L.up[o + k] >= 1;
-            else if (pk > k) ok = ok && allowed(L, o + k, o + pk);
-        }
-        const bool all = __ballot(!ok) == 0;
-        if (lane == 0) L.mat[o] = all ? 1 : 0;
-    }
-}
 // q5[0..4]: no pair fits (one thread)
 template <class LT>
 __device__ __forceinline__ void q5_start(const LT &L, int N) {

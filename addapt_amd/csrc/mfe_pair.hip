@@ -238,7 +238,7 @@ __device__ __forceinline__ void cell_pass(const CP &L, const Band &bd, int lane,
         al = al && (pi ? pi == j : (pj ? pj == i : (wi[q] >> 24) == (wj[q] >> 24)));
         pr[q] = inb[q] && ty[q] != 0 && al;
         const int sim = wim[q] & 7, sjp = wjp[q] & 7, si1 = wi1[q] & 7, sjm = wjm[q] & 7;
-        ix1[q] = (d - 1 == 3) ? DT_TAU + ty[q] : DT_MMH + ty[q] * 25 + si1 * 5 + sjm;
+        ix1[q] = hairpin_dt_index(d - 1, ty[q], si1, sjm);
         f1[q] = L.dt[ix1[q]];
         f2[q] = L.dt[DT_MLS + ty[q] * 25 + sim * 5 + sjp];
     }
@@ -347,16 +347,13 @@ __device__ __forceinline__ bool pair_setup(const KArgs &ka, const DevScaled *__r
     const int kp = min(tid, np - 1);
     uint8_t v_sw, v_up, v_dn, v_pt, v_en, v_fl;
     {
-        const uint8_t *bef = nullptr, *aft = nullptr;
-        int blen = 0;
+        SeqSrc src{nullptr, raw, nullptr, 0, ka.Nraw};   // seq_src() through gld
         if (V.ctx >= 0) {
-            bef = ka.ctx_seq + gld(ka.ctx_off + 4 * V.ctx + 0);
-            blen = gld(ka.ctx_off + 4 * V.ctx + 1);
-            aft = ka.ctx_seq + gld(ka.ctx_off + 4 * V.ctx + 2);
+            src.bef = ka.ctx_seq + gld(ka.ctx_off + 4 * V.ctx + 0);
+            src.blen = gld(ka.ctx_off + 4 * V.ctx + 1);
+            src.aft = ka.ctx_seq + gld(ka.ctx_off + 4 * V.ctx + 2);
         }
-        const int pp = (kp == 0 ? N : (kp == N + 1 ? 1 : kp)) - 1;
-        const uint8_t *sp = pp < blen ? bef + pp : (pp < blen + ka.Nraw ? raw + (pp - blen) : aft + (pp - blen - ka.Nraw));
-        v_sw = gld(sp);
+        v_sw = gld(src.at(wrap_pos(kp, N) - 1));
         v_up = gld(cons + uint32_t(kp));
         v_dn = gld(cons + uint32_t(np + kp));
         v_pt = gld(cons + uint32_t(2 * np + kp));
@@ -438,8 +435,9 @@ __device__ __forceinline__ bool pair_setup(const KArgs &ka, const DevScaled *__r
     const unsigned long long st_s2 = __builtin_amdgcn_s_memtime();   // sequence, constraints
 #endif
     if ((mh0 || mh1) && mL > 0) {
-        // lanes = starts; the motif's positions in chunks of 8 independent reads (one
-        // LDS round trip per chunk, not one per position of the longest match)
+        // fold_common.hpp motif_scan, open-coded: lanes = starts; the motif's positions in
+        // chunks of 8 independent reads (one LDS round trip per chunk, not one per
+        // position of the longest match)
         for (int o0 = 1 + wid * WAVE; o0 + mL - 1 <= N; o0 += NT) {
             const int o = o0 + lane;
             const bool in = o + mL - 1 <= N;
@@ -458,7 +456,7 @@ __device__ __forceinline__ bool pair_setup(const KArgs &ka, const DevScaled *__r
             if (in) L.mat[o] = ok ? 1 : 0;
         }
         __syncthreads();
-        motif_constraints(L, mpt, mL, N, wid, lane);
+        motif_constraints<NWV>(L, mpt, mL, N, wid, lane);
     }
 #ifdef ADX_STAMP
     const unsigned long long st_s25 = __builtin_amdgcn_s_memtime();   // motif scan done

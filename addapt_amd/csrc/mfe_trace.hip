@@ -68,50 +68,15 @@ mfe_trace_kernel(KArgs ka, int variant, const uint8_t *__restrict__ seqs, int w0
                   ei(X->mlclosing), ei(X->mlbase_sig), ei(X->motif_extra), X->motif_len, V.motif != 0};
 
     // ---- sequence (context-padded), constraint arrays, special hairpins, motif
-    const uint8_t *raw = seqs + size_t(w) * ka.Nraw;
-    const uint8_t *cons = ka.cons + V.cons_off;
-    const uint8_t *bef = nullptr, *aft = nullptr;
-    int blen = 0;
-    if (V.ctx >= 0) {
-        bef = ka.ctx_seq + ka.ctx_off[4 * V.ctx + 0];
-        blen = ka.ctx_off[4 * V.ctx + 1];
-        aft = ka.ctx_seq + ka.ctx_off[4 * V.ctx + 2];
-    }
-    for (int k = tid; k < np; k += TR_NT) {
-        uint8_t s = 0;
-        if (k >= 1 && k <= N) {
-            const int pp = k - 1;
-            if (pp < blen) s = bef[pp];
-            else if (pp < blen + ka.Nraw) s = raw[pp - blen];
-            else s = aft[pp - blen - ka.Nraw];
-        }
-        L.S[k] = s;
-        L.up[k] = cons[k];
-        L.ptn[k] = cons[2 * np + k];
-        L.enc[k] = cons[3 * np + k];
-        L.flg[k] = cons[4 * np + k];
-        L.mat[k] = 0;
-        L.out[k] = '.';
-    }
-    for (int k = tid; k < MAX_SPECIAL_HP; k += TR_NT) {
-        const bool on = k < X->n_special;
-        L.spk[k] = on ? X->sp_key[k] : 0xFFFFFFFFu;   // hp_key never sets the top bits
-        L.spv[k] = on ? ei(X->sp_val[k]) : TR_INF;
-    }
-    for (int k = tid; k < MAX_MOTIF; k += TR_NT) {
-        L.mcode[k] = X->motif_code[k];
-        L.mpt[k] = X->motif_pt[k];
-    }
-    __syncthreads();
+    // sites (fold_common.hpp seq_setup), then the trace's own start values
+    for (int k = tid; k < np; k += TR_NT) L.out[k] = '.';
+    seq_setup<TR_NT>(L, ka, V, seqs + size_t(w) * ka.Nraw, tid,
+                     [](bool on, float v) { return on ? ei(v) : TR_INF; });
     if (tid == 0) {
-        L.S[0] = L.S[N];   // ViennaRNA's S1 wrap-around
-        L.S[N + 1] = L.S[1];
         L.f5[0] = 0;
         L.top = 0;
         L.red = f5_unpaired(L, 1);
     }
-    if (M.holo && M.mL > 0)
-        for (int o = tid + 1; o + M.mL - 1 <= N; o += TR_NT) L.mat[o] = M.motif_site(o) ? 1 : 0;
     __syncthreads();
 
     // ---- fill: one anti-diagonal per barrier, then f5 left to right

@@ -2,14 +2,17 @@
 // Zuker fill, one lane's share of a traceback item's candidates, and what the
 // winning candidate pushes.  Free of HIP builtins: the kernel supplies the
 // barriers and the LDS atomicMin between them, so a host program can run the
-// same code lane by lane against the CPU oracle.  The includer provides off(),
-// ptype(), rtype(), allowed() and special_hp() (fold_common.hpp) in namespace
-// adx and defines TR_FN (the kernel: __device__).
+// same code lane by lane against the CPU oracle.  off(), ptype(), rtype() and
+// allowed() come from fold_setup_core.hpp, which a host program can include
+// too; the includer provides special_hp() (fold_common.hpp; on a host, any
+// scan of the keys that returns the last match) in namespace adx before this
+// header and defines TR_FN (the kernel: __device__).
 #pragma once
 
 #include <cstdint>
 
 #include "dev_types.hpp"
+#include "fold_setup_core.hpp"
 
 namespace adx {
 namespace {
@@ -103,19 +106,8 @@ struct Trace {
         return cpq + e_int(n1, n2, t, type(q, p), L.S[i + 1], L.S[j - 1], L.S[p - 1], L.S[q + 1]);
     }
     TR_FN int ml_closing(int i, int j, int t) const { return mlclosing + mlstem(rtype(t), L.S[j - 1], L.S[i + 1]); }
+    // L.mat[o]: fold_setup_core.hpp motif_site at start o (fold_common.hpp seq_setup)
     TR_FN bool motif_at(int i, int j) const { return holo && mL > 0 && j - i == mL - 1 && L.mat[i] != 0; }
-
-    // Is the motif formable with its outer pair at (o, o + mL - 1)?  (oracle/fold.c
-    // motif_at: the sequence matches, the constraint admits every motif pair and
-    // every unpaired motif base)
-    TR_FN bool motif_site(int o) const {
-        for (int k = 0; k < mL; k++) {
-            const int pk = L.mpt[k];
-            if (L.S[o + k] != L.mcode[k]) return false;
-            if (pk < 0 ? L.up[o + k] < 1 : (pk > k && !allowed(L, o + k, o + pk))) return false;
-        }
-        return true;
-    }
 
     // ---- fill: c, fm1, fm of one cell (every shorter span is finished)
     TR_FN void fill_cell(int i, int j) const {

@@ -317,10 +317,6 @@ __device__ __forceinline__ void ox_run(const typename OxBlk<U>::T &z, const OxL 
         z.run(L, c, d, umax, ctb, outer, g, sp);
     }
 }
-__device__ __forceinline__ float quad_sum_f(float v) {   // sum over the 4 lanes of a quad, in every lane
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xb1, 0xf, 0xf, false));   // [1,0,3,2]
-    return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4e, 0xf, 0xf, false));   // [2,3,0,1]
-}
 
 // B: the interior-loop gather of every diagonal for one block of loop sizes
 // (-1 = none), the block's shape factors held in registers for the whole sweep;
@@ -381,7 +377,7 @@ __device__ __forceinline__ void b_sweep(const OxL &L, int N, int lane, Wid wid, 
             ox_run<U4>(s4, L, c, d, umax, ty2, ctb, outer, g, sp, gs, sps, r);
             OSTAMP(3);   // B shapes
             // small sizes count once (phase 0), then the cell's total over its four lanes
-            const float part = quad_sum_f(fmaf(g, c.mmin, sp) + (r == 0 ? fmaf(gs, c.mmin, sps) : 0.f));
+            const float part = quad_sum(fmaf(g, c.mmin, sp) + (r == 0 ? fmaf(gs, c.mmin, sps) : 0.f));
             if (r == 0 && idx < ncell && (tp >> 16))   // the cell's natural slot (F reads lane = cell)
                 L.part[((par * NSETS + ((i - 1) >> 6)) * OX_NB + wid) * WAVE + ((i - 1) & (WAVE - 1))] = part;
         }
@@ -402,26 +398,8 @@ __device__ __forceinline__ void ox_setup(const OxL &L, const KArgs &ka, const De
                                          const uint8_t *seqs, int w, const float *q5g, int N, int tid) {
     const DevTables &T = *ka.T;
     const int NP = L.NP;
-    {
-        const uint8_t *bef = nullptr, *aft = nullptr;
-        int blen = 0;
-        if (V.ctx >= 0) {
-            bef = ka.ctx_seq + ka.ctx_off[4 * V.ctx + 0];
-            blen = ka.ctx_off[4 * V.ctx + 1];
-            aft = ka.ctx_seq + ka.ctx_off[4 * V.ctx + 2];
-        }
-        const uint8_t *raw = seqs + size_t(w) * ka.Nraw;
-        for (int k = tid; k < NP; k += OX_NT) {
-            uint8_t s = 0;
-            if (k >= 1 && k <= N) {
-                const int pp = k - 1;
-                if (pp < blen) s = bef[pp];
-                else if (pp < blen + ka.Nraw) s = raw[pp - blen];
-                else s = aft[pp - blen - ka.Nraw];
-            }
-            L.S[k] = s;
-        }
-    }
+    const SeqSrc src = seq_src(ka, V, seqs + size_t(w) * ka.Nraw);
+    for (int k = tid; k < NP; k += OX_NT) L.S[k] = src.code(k, N);
     for (int k = tid; k < CT_SIZE; k += OX_NT) L.ct[k] = XS->ctab[k];
     for (int k = tid; k < 200; k += OX_NT) {
         L.dt[DT_MMI + k] = (&T.mmI[0][0][0])[k];
@@ -429,31 +407,15 @@ __device__ __forceinline__ void ox_setup(const OxL &L, const KArgs &ka, const De
     }
     for (int k = tid; k < 288; k += OX_NT) L.dt[DT_EXT + k] = (&T.ext[0][0][0])[k];
     for (int k = tid; k < 31 * 32; k += OX_NT) {
-        const int u = k >> 5, n1 = k & 31, n2 = u - n1;
-        float f = 0.f;
-        if (n1 <= u) {
-            const int kd = loop_kind(n1, n2);
-            f = kd < 0 ? XS->fgen[(u - 6) * FG_ROW + n1 - 2]
-              : kd == TK_STK ? XS->ctab[CT_FSM + 0]
-              : kd == TK_B1 ? XS->ctab[CT_FSM + 1]
-              : kd == TK_BUL ? XS->ctab[CT_FB + u]
-              : kd == TK_1N ? XS->ctab[CT_F1N + u - 1]
-              : kd == TK_I11 ? XS->ctab[CT_FSM + 2]
-              : kd == TK_I22 ? XS->ctab[CT_FSM + 4]
-              : kd == TK_M23 ? XS->ctab[CT_FSM + 5]
-              : XS->ctab[CT_FSM + 3];   // 1x2 / 2x1
-        }
-        L.sf[k] = f;
+        const int u = k >> 5, n1 = k & 31;
+        L.sf[k] = n1 <= u ? shape_factor(XS, u, n1) : 0.f;
     }
     for (int k = tid; k <= N; k += OX_NT) L.q5[k] = q5g[k];
     for (int k = tid; k < 2 * NP; k += OX_NT) L.rq[k] = L.rr[k] = L.r1[k] = 0.f;
     for (int k = tid; k < NP; k += OX_NT) { L.q5b[k] = 0.f; L.pm[k] = 0.f; L.mat[k] = 0; }
     for (int k = tid; k < OX_MAXP; k += OX_NT) L.pd[k] = 0.0;
     __syncthreads();
-    if (tid == 0) {
-        L.S[0] = L.S[N];
-        L.S[N + 1] = L.S[1];
-    }
+    if (tid == 0) wrap_ends(L, N);
     __syncthreads();
 }
 
@@ -535,11 +497,7 @@ __device__ __forceinline__ void ox_ext_adjoint(const OxL &L, const float *G, con
 
 // motif sites (unconstrained: the sequence alone decides), one wave
 __device__ __forceinline__ void ox_motif_sites(const OxL &L, const DevScaled *XS, int N, int mL, int lane) {
-    for (int o = lane + 1; o + mL - 1 <= N; o += WAVE) {
-        bool ok = true;
-        for (int k = 0; k < mL && ok; k++) ok = L.S[o + k] == XS->motif_code[k];
-        L.mat[o] = ok ? 1 : 0;
-    }
+    motif_scan<WAVE>(L, XS->motif_code, mL, N, lane);
 }
 
 // While wave 0 runs the exterior adjoint: the window zeroed and the pairable

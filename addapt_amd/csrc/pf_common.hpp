@@ -25,8 +25,6 @@
 namespace adx {
 namespace {
 
-typedef float f2 __attribute__((ext_vector_type(2)));
-
 constexpr int PF_NMW = 4;     // qm item waves
 constexpr int PF_RF = 8;      // record fields (rec_store): word, mmo, mo, m23, 1x1..2x2 factors
 constexpr int PF_SLACK = 16;
@@ -48,22 +46,6 @@ __device__ __forceinline__ f2 vfma_s(f2 v, float f, f2 g) { return f2{fmaf(v.x, 
 // the non-pairable mark (-0; a finished cell never takes it)
 __device__ __forceinline__ bool is_mark(float v) { return __float_as_uint(v) == 0x80000000u; }
 __device__ __forceinline__ bool is_mark(f2 v) { return __float_as_uint(v.x) == 0x80000000u; }
-// v + (v of the lane DPP control CTRL selects; 0 where it selects none)
-template <int CTRL>
-__device__ __forceinline__ float dpp_add(float v) {
-    return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false));
-}
-template <int CTRL>
-__device__ __forceinline__ f2 dpp_add(f2 v) {
-    const float x = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v.x), CTRL, 0xf, 0xf, false));
-    const float y = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v.y), CTRL, 0xf, 0xf, false));
-    return v + f2{x, y};
-}
-template <class V>
-__device__ __forceinline__ V quad_sum(V v) {   // sum over the 4 lanes of a quad, in every lane
-    v = dpp_add<0xb1>(v);      // quad_perm [1,0,3,2]
-    return dpp_add<0x4e>(v);   // quad_perm [2,3,0,1]
-}
 
 // Diagnostic builds (-DADX_STAMP): the kernel's stamp locals, handed to the helpers that stamp
 #ifdef ADX_STAMP
@@ -128,21 +110,6 @@ __device__ __forceinline__ PfL<typename K::V> pf_carve(char *smem, const Lay &Y,
 }
 
 // ---------------------------------------------------------------- interior-loop shapes
-// constant factor of shape (u, n1) (setup_core.hpp addS / fgen)
-__device__ __forceinline__ float shape_factor(const DevScaled *XS, int u, int n1) {
-    const int kd = loop_kind(n1, u - n1);
-    const float *p = kd < 0 ? XS->fgen + (u - 6) * FG_ROW + n1 - 2
-                   : kd == TK_STK ? XS->ctab + CT_FSM + 0
-                   : kd == TK_B1 ? XS->ctab + CT_FSM + 1
-                   : kd == TK_BUL ? XS->ctab + CT_FB + u
-                   : kd == TK_1N ? XS->ctab + CT_F1N + u - 1
-                   : kd == TK_I11 ? XS->ctab + CT_FSM + 2
-                   : kd == TK_I22 ? XS->ctab + CT_FSM + 4
-                   : kd == TK_M23 ? XS->ctab + CT_FSM + 5
-                   : XS->ctab + CT_FSM + 3;
-    return *p;
-}
-
 struct PfCell {              // per lane: the closing pair (i, i+s)
     int i, ty8, A, B;
     float tau, mo, m23;
@@ -415,17 +382,8 @@ __device__ __forceinline__ PfSetup<pf_nct<K>()> pf_setup_load(const KArgs &ka, c
     u.mp = XS->motif_pt[min(tid, MAX_MOTIF - 1)];
     const uint8_t *cons = ka.cons + V.cons_off;
     const int kp = min(tid, NP - 1);   // this thread's position
-    const uint8_t *bef = nullptr, *aft = nullptr;
-    int blen = 0;
-    if (V.ctx >= 0) {
-        bef = ka.ctx_seq + ka.ctx_off[4 * V.ctx + 0];
-        blen = ka.ctx_off[4 * V.ctx + 1];
-        aft = ka.ctx_seq + ka.ctx_off[4 * V.ctx + 2];
-    }
-    const uint8_t *raw = seqs + size_t(w) * ka.Nraw;
-    const int pp = kp >= 1 && kp <= N ? kp - 1 : blen;   // outside 1..N: a valid byte, discarded
-    const uint8_t *sp = pp < blen ? bef + pp : (pp < blen + ka.Nraw ? raw + (pp - blen) : aft + (pp - blen - ka.Nraw));
-    u.s = *sp;
+    const SeqSrc src = seq_src(ka, V, seqs + size_t(w) * ka.Nraw);
+    u.s = *src.at(kp >= 1 && kp <= N ? kp - 1 : src.blen);   // outside 1..N: a valid byte, discarded
     u.up = cons[kp];
     u.dn = cons[NP + kp];
     u.pt = cons[2 * NP + kp];
@@ -478,29 +436,12 @@ template <class K>
 __device__ __forceinline__ void pf_motif_sites(const PfL<typename K::V> &L, bool any_motif, int mL, int tid, int lane,
                                                int wid) {
     const int N = L.N;
-    if (tid == 0) {
-        L.S[0] = L.S[N];
-        L.S[N + 1] = L.S[1];
-    }
+    if (tid == 0) wrap_ends(L, N);
     __syncthreads();
     if (any_motif) {
-        for (int o = tid + 1; o + mL - 1 <= N; o += K::NT) {
-            bool ok = true;
-            for (int k = 0; k < mL && ok; k++) ok = L.S[o + k] == L.mcode[k];
-            L.mat[o] = ok ? 1 : 0;
-        }
+        motif_scan<K::NT>(L, L.mcode, mL, N, tid);
         __syncthreads();
-        for (int o = 1 + wid; o + mL - 1 <= N; o += K::NW) {
-            if (!uni(L.mat[o])) continue;
-            bool ok = true;
-            for (int k = lane; k < mL; k += WAVE) {
-                const int pk = L.mpt[k];
-                if (pk < 0) ok = ok && L.up[o + k] >= 1;
-                else if (pk > k) ok = ok && allowed(L, o + k, o + pk);
-            }
-            const bool all = __ballot(!ok) == 0;
-            if (lane == 0) L.mat[o] = all ? 1 : 0;
-        }
+        motif_constraints<K::NW>(L, L.mpt, mL, N, wid, lane);
     }
 }
 
@@ -526,6 +467,8 @@ __device__ __forceinline__ typename K::V pf_hairpin_init(const PfL<typename K::V
             }
         }
         if (!special)
+            // L.dt[hairpin_dt_index(u, type, S[i+1], S[j-1])], open-coded as a select between two
+            // loads (the index form cost pf_cells_kernel 0.3 %, profiles/fold_setup_ab.txt)
             h = K::hp_len(L, hpl, D, wid) *
                 ((u == 3) ? L.dt[DT_TAU + type] : L.dt[DT_MMH + type * 25 + S[i + 1] * 5 + S[j - 1]]);
     }

@@ -58,56 +58,11 @@ struct SampleLds {
 };
 static_assert(sizeof(FillLds) <= 48 * 1024 && sizeof(SampleLds) <= 48 * 1024, "static LDS of the pf_sample kernels");
 
-// The sequence (context-padded exactly as mfe_trace_kernel reads it), the
-// variant's constraint arrays, the special hairpins and the motif sites into
-// LDS; ends with a barrier.
+// The sequence (context-padded), the variant's constraint arrays, the special
+// hairpins and the motif sites into LDS, exactly as mfe_trace_kernel gets them
+// (fold_common.hpp seq_setup); ends with a barrier.
 __device__ void load_sequence(PfSeqLds &L, const KArgs &ka, const DevVariant &V, const uint8_t *raw, int tid) {
-    const DevScaled *X = ka.X;
-    const int N = V.N, np = N + 2;
-    const uint8_t *cons = ka.cons + V.cons_off;
-    const uint8_t *bef = nullptr, *aft = nullptr;
-    int blen = 0;
-    if (V.ctx >= 0) {
-        bef = ka.ctx_seq + ka.ctx_off[4 * V.ctx + 0];
-        blen = ka.ctx_off[4 * V.ctx + 1];
-        aft = ka.ctx_seq + ka.ctx_off[4 * V.ctx + 2];
-    }
-    for (int k = tid; k < np; k += PS_NT) {
-        uint8_t s = 0;
-        if (k >= 1 && k <= N) {
-            const int pp = k - 1;
-            if (pp < blen) s = bef[pp];
-            else if (pp < blen + ka.Nraw) s = raw[pp - blen];
-            else s = aft[pp - blen - ka.Nraw];
-        }
-        L.S[k] = s;
-        L.up[k] = cons[k];
-        L.ptn[k] = cons[2 * np + k];
-        L.enc[k] = cons[3 * np + k];
-        L.flg[k] = cons[4 * np + k];
-        L.mat[k] = 0;
-    }
-    for (int k = tid; k < MAX_SPECIAL_HP; k += PS_NT) {
-        const bool on = k < X->n_special;
-        L.spk[k] = on ? X->sp_key[k] : 0xFFFFFFFFu;   // hp_key never sets the top bits
-        L.spv[k] = on ? X->sp_val[k] : 0.f;
-    }
-    for (int k = tid; k < MAX_MOTIF; k += PS_NT) {
-        L.mcode[k] = X->motif_code[k];
-        L.mpt[k] = X->motif_pt[k];
-    }
-    __syncthreads();
-    if (tid == 0) {
-        L.S[0] = L.S[N];   // ViennaRNA's S1 wrap-around
-        L.S[N + 1] = L.S[1];
-    }
-    __syncthreads();
-    const int mL = X->motif_len;
-    if (V.motif != 0 && mL > 0) {
-        const PfModel M{ka.T, X, L, nullptr, nullptr, nullptr, nullptr, N, mL, true};
-        for (int o = tid + 1; o + mL - 1 <= N; o += PS_NT) L.mat[o] = M.motif_site(o) ? 1 : 0;
-    }
-    __syncthreads();
+    seq_setup<PS_NT>(L, ka, V, raw, tid, [](bool on, float v) { return on ? v : 0.f; });
 }
 
 __device__ __forceinline__ double wave_sum(double v) {

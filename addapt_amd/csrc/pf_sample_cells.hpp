@@ -2,9 +2,10 @@
 // the weight of every candidate of every item kind.  The fill sums an item's
 // candidate weights into its table entry and the sampler draws among the same
 // weights, so the two decompositions agree term for term by construction.
-// Free of HIP builtins, in mfe_trace_core.hpp's style: the includer provides
-// off(), ptype(), rtype(), allowed() and special_hp() (fold_common.hpp) in
-// namespace adx and defines TR_FN (the kernels: __device__).
+// Free of HIP builtins, in mfe_trace_core.hpp's style: off(), ptype(), rtype()
+// and allowed() come from fold_setup_core.hpp; the includer provides
+// special_hp() (fold_common.hpp) in namespace adx before this header and
+// defines TR_FN (the kernels: __device__).
 //
 // The recursion is oracle/fold.c pf_inside with the context's FP32 factors
 // (DevTables / DevScaled, every factor carrying sigma per covered nucleotide),
@@ -20,6 +21,7 @@
 #include <cstdint>
 
 #include "dev_types.hpp"
+#include "fold_setup_core.hpp"
 
 namespace adx {
 namespace {
@@ -58,17 +60,8 @@ struct PfModel {
     TR_FN bool can_pair(int i, int j) const { return j - i >= 4 && type(i, j) != 0 && allowed(L, i, j); }
     TR_FN double mlstem(int t, int n5, int n3) const { return T->mlstem[t][n5][n3]; }
     TR_FN double ext(int t, int k, int j) const { return T->ext[t][k > 1 ? L.S[k - 1] : 5][j < N ? L.S[j + 1] : 5]; }
+    // L.mat[o]: fold_setup_core.hpp motif_site at start o (fold_common.hpp seq_setup)
     TR_FN bool motif_at(int i, int j) const { return holo && mL > 0 && j - i == mL - 1 && L.mat[i] != 0; }
-
-    // as mfe_trace_core.hpp motif_site (oracle/fold.c motif_at)
-    TR_FN bool motif_site(int o) const {
-        for (int k = 0; k < mL; k++) {
-            const int pk = L.mpt[k];
-            if (L.S[o + k] != L.mcode[k]) return false;
-            if (pk < 0 ? L.up[o + k] < 1 : (pk > k && !allowed(L, o + k, o + pk))) return false;
-        }
-        return true;
-    }
 
     TR_FN double hairpin(int i, int j, int t) const {
         const int u = j - i - 1;
