@@ -27,14 +27,14 @@ __global__ void combine_kernel(KArgs ka, int W, const int *mask, double *scores,
     const double *pp = ka.pair_p ? ka.pair_p + size_t(w) * ka.n_pairs : nullptr;
     const int nt = ka.n_terms * ka.n_ctx_eff;
     double *tv = terms ? terms + size_t(w) * nt : nullptr;
-    double score = 0.0;
+    ContextSum score{ka.n_terms};
     for (int idx = 0; idx < nt; idx++) {
         double wt;
         const double val = term_value(ka, g, pp, idx, wt);
         if (tv) tv[idx] = val;
-        score += wt * val;
+        score.add(wt * val);
     }
-    scores[w] = score;
+    scores[w] = score.sum();
 }
 
 hipError_t launch_combine(const KArgs &ka, int W, const int *mask, double *scores, double *terms,

@@ -1118,6 +1118,7 @@ __device__ double combine_score(const KArgs &ka, const Lds<P> &L, const double *
     const DevScaled &X = *ka.X;
     double score = 0.0;
     for (int c = 0; c < ka.n_ctx_eff; c++) {
+        double part = 0.0;   // the reference adds each context's sum (scoring.cc:124-130; combine.hpp ContextSum)
         for (int t = 0; t < ka.n_terms; t++) {
             const DevTermMap m = ka.tmap[c * ka.n_terms + t];
             double p;
@@ -1134,8 +1135,9 @@ __device__ double combine_score(const KArgs &ka, const Lds<P> &L, const double *
             if (!m.favorable) p = 1.0 - p;
             const double val = log(p);
             if (terms_out) terms_out[c * ka.n_terms + t] = val;
-            score += m.weight * val;
+            part += m.weight * val;
         }
+        score += part;
     }
     return score;
 }
