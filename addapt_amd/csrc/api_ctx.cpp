@@ -686,6 +686,50 @@ extern "C" adx_status adx_last_sample_ms(const adx_ctx *c, double *fill_ms, doub
     return ADX_OK;
 }
 
+// energies, probabilities and status bytes of n_per structures per device sequence for variant v
+static adx_status eval_structures(adx_ctx *c, const char *who, const uint8_t *dseqs, int W, int v, int n_per,
+                                  const char *structures, bool shared, double *energies, double *probs,
+                                  uint8_t *status) {
+    Problem &pb = c->pb;
+    if (v < 0 || v >= static_cast<int>(pb.variants.size()))
+        return fail(ADX_EINVAL, "%s: variant %d outside [0, %zu)", who, v, pb.variants.size());
+    if (n_per < 1) return fail(ADX_EINVAL, "%s: %d structures per sequence < 1", who, n_per);
+    if (probs && pb.mode != ADX_FOLD_PF)
+        return fail(ADX_EUNSUPPORTED, "%s: probabilities on ADX_FOLD_PF contexts only (an MFE context holds no "
+                    "Boltzmann factors; use adx_fold_eval_structures)", who);
+    const size_t L = size_t(pb.variants[v].N);
+    if (size_t(W) > SIZE_MAX / L / size_t(n_per) / sizeof(double))
+        return fail(ADX_EINVAL, "%s: %d x %d structures of %zu chars overflow", who, W, n_per, L);
+    return pb.eval_structures(dseqs, W, v, n_per, structures, shared, energies, probs, status);
+}
+
+extern "C" adx_status adx_eval_structures_batch(adx_ctx *c, int W, const char *seqs, int variant, int n_per_seq,
+                                                const char *structures, double *energies, double *probs,
+                                                uint8_t *status) {
+    if (!c || W <= 0 || !seqs || !structures || !energies)
+        return fail(ADX_EINVAL, "adx_eval_structures_batch: bad argument");
+    Problem &pb = c->pb;
+    DevBuf<uint8_t> dseq;
+    if (adx_status su = upload_codes(seqs, size_t(W) * pb.Nraw, dseq, pb.stream)) return su;
+    return eval_structures(c, "adx_eval_structures_batch", dseq.p, W, variant, n_per_seq, structures, false, energies,
+                           probs, status);
+}
+
+extern "C" adx_status adx_walkers_eval_structures(adx_ctx *c, int variant, int n_structs, const char *structures,
+                                                  double *energies, double *probs, uint8_t *status) {
+    if (!c || !structures || !energies) return fail(ADX_EINVAL, "adx_walkers_eval_structures: null argument");
+    if (c->W <= 0) return fail(ADX_ESTATE, "adx_walkers_eval_structures before adx_walkers_init");
+    return eval_structures(c, "adx_walkers_eval_structures", c->cur_seq.p, c->W, variant, n_structs, structures, true,
+                           energies, probs, status);
+}
+
+extern "C" adx_status adx_last_eval_ms(const adx_ctx *c, double *fill_ms, double *eval_ms) {
+    if (!c || !fill_ms || !eval_ms) return fail(ADX_EINVAL, "adx_last_eval_ms: null argument");
+    *fill_ms = c->pb.eval_fill_ms;
+    *eval_ms = c->pb.eval_ms;
+    return ADX_OK;
+}
+
 // centroid and MEA structures of W device sequences for the (context, condition) unconstrained fold
 static adx_status ensemble_structures(adx_ctx *c, const char *who, const uint8_t *dseqs, int W, int condition,
                                       int context, double gamma, char *centroid, char *mea,

@@ -211,6 +211,25 @@ extern "C" adx_status adx_fold_sample_structures(adx_fold *f, int n_samples, uin
     return pb.sample("adx_fold_sample_structures", dseq.p, 1, 0, n_samples, seed, structures, energy);
 }
 
+extern "C" adx_status adx_fold_eval_structures(adx_fold *f, int convention, int n, const char *structures,
+                                               double *energies, double *probs, uint8_t *status) {
+    if (!f || !structures || !energies) return fail(ADX_EINVAL, "adx_fold_eval_structures: null argument");
+    if (convention != ADX_FOLD_PF && convention != ADX_FOLD_MFE)
+        return fail(ADX_EINVAL, "adx_fold_eval_structures: convention %d is neither ADX_FOLD_PF nor ADX_FOLD_MFE",
+                    convention);
+    if (n < 1) return fail(ADX_EINVAL, "adx_fold_eval_structures: n %d < 1", n);
+    if (probs && convention != ADX_FOLD_PF)
+        return fail(ADX_EINVAL, "adx_fold_eval_structures: probabilities exist in the ADX_FOLD_PF convention only");
+    Problem pb;
+    // the default scale serves the probabilities: pf_fill_kernel sums in FP64
+    adx_status s = fold_problem(f, convention, pb);
+    if (s) return s;
+    DevBuf<uint8_t> dseq;
+    s = upload_codes(f->seq.data(), f->seq.size(), dseq, pb.stream);
+    if (s) return s;
+    return pb.eval_structures(dseq.p, 1, 0, n, structures, true, energies, probs, status);
+}
+
 extern "C" adx_status adx_fold_bpp(adx_fold *f, int i, int j, double *prob) {
     if (!f || !prob) return fail(ADX_EINVAL, "adx_fold_bpp: null argument");
     const int N = static_cast<int>(f->seq.size());

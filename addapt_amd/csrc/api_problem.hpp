@@ -64,6 +64,9 @@ struct Problem : DeviceStream {
     DevBuf<double> dSample;      // qb / qm / qm1 / q5 scratch of pf_fill_kernel, one launch chunk
     float sample_fill_ms = 0.f, sample_draw_ms = 0.f;   // the last sample() call, from HIP events
     float ens_bppm_ms = 0.f, ens_struct_ms = 0.f;       // the last ensemble() call, from HIP events
+    DevBuf<DevTables> dTE;       // struct_eval_kernel: energy-valued tables of a PF problem (an MFE problem's dT serves)
+    DevBuf<EvalTab> dEval;       // and the convention's loop-length table (setup_core.hpp build_eval_tab)
+    float eval_fill_ms = 0.f, eval_ms = 0.f;            // the last eval_structures() call, from HIP events
     size_t tab_slot = 0;
     bool state_on = false;   // set for MC launches only (not for adx_score_batch)
     std::unique_ptr<DevTables> hT;
@@ -374,6 +377,75 @@ struct Problem : DeviceStream {
             ens_bppm_ms += a;
             ens_struct_ms += b;
         }
+        return ADX_OK;
+    }
+
+    // struct_eval_kernel's tables in this problem's convention (PF or MFE), uploaded once
+    adx_status ensure_eval() {
+        if (dEval.p) return ADX_OK;
+        auto E = std::make_unique<EvalTab>();
+        build_eval_tab(*P, motif, motif_eint, *E, mode == 1);
+        if (mode != 1) {
+            auto TE = std::make_unique<DevTables>();
+            build_tables(*P, *TE, true);
+            HIP_TRY(dTE.upload(TE.get(), 1, stream));
+        }
+        HIP_TRY(dEval.upload(E.get(), 1, stream));
+        HIP_TRY(hipStreamSynchronize(stream));   // E and TE are locals
+        return ADX_OK;
+    }
+
+    // Energies, probabilities and status bytes of n_per given structures for each of W
+    // sequences (device codes) under variant v, to HOST buffers of W * n_per,
+    // sequence-major (probs and status optional; probs on PF problems only).
+    // structures (host): W * n_per * L chars, or n_per * L shared by every sequence.
+    // struct_eval.hip; probs adds pf_fill_kernel's FP64 fill per sequence.  Every
+    // buffer is the call's own but the fill scratch: no fold state is touched.
+    // ADX_EVAL_CHUNK=<n> (tests) bounds the sequences per launch; the results do not depend on it.
+    adx_status eval_structures(const uint8_t *dseqs, int W, int v, int n_per, const char *structures, bool shared,
+                               double *energies, double *probs, uint8_t *status) {
+        if (adx_status se = ensure_eval()) return se;
+        const KArgs ka = kargs();
+        const size_t L = size_t(variants[v].N);
+        const size_t items = size_t(W) * n_per;
+        int per = std::min(W, 65535);   // grid.y of struct_eval_kernel
+        if (probs) per = std::min(per, pf_sample_plan(ka, int(L), W, 1).seqs);
+        if (const char *env = std::getenv("ADX_EVAL_CHUNK"))
+            if (std::atoi(env) > 0) per = std::min(per, std::atoi(env));
+        const size_t slice = pf_sample_slice_doubles(ka);
+        if (probs && dSample.n < size_t(per) * slice) HIP_TRY(dSample.alloc(size_t(per) * slice));
+        DevBuf<char> dst;
+        DevBuf<double> de, dp;
+        DevBuf<uint8_t> ds;
+        HIP_TRY(dst.upload(structures, (shared ? size_t(n_per) : items) * L, stream));
+        HIP_TRY(de.alloc(items));
+        if (probs) HIP_TRY(dp.alloc(items));
+        if (status) HIP_TRY(ds.alloc(items));
+        Events ev;
+        if (adx_status se = ev.create(3)) return se;
+        eval_fill_ms = eval_ms = 0.f;
+        const size_t stride = shared ? 0 : size_t(n_per) * L;
+        for (int w0 = 0; w0 < W; w0 += per) {
+            const int n = std::min(per, W - w0);
+            HIP_TRY(hipEventRecord(ev[0], stream));
+            if (probs) HIP_TRY(launch_pf_fill(ka, v, dseqs, w0, n, dSample.p, nullptr, stream));
+            HIP_TRY(hipEventRecord(ev[1], stream));
+            HIP_TRY(launch_struct_eval(ka, mode == 1 ? dT.p : dTE.p, dEval.p, v, dseqs, w0, n, n_per,
+                                       dst.p + size_t(w0) * stride, stride, probs ? dSample.p : nullptr,
+                                       size_t(w0) * n_per, de.p, probs ? dp.p : nullptr, status ? ds.p : nullptr,
+                                       stream));
+            HIP_TRY(hipEventRecord(ev[2], stream));
+            HIP_TRY(hipStreamSynchronize(stream));   // the fill scratch is reused by the next chunk
+            float a = 0.f, b = 0.f;
+            HIP_TRY(hipEventElapsedTime(&a, ev[0], ev[1]));
+            HIP_TRY(hipEventElapsedTime(&b, ev[1], ev[2]));
+            if (probs) eval_fill_ms += a;
+            eval_ms += b;
+        }
+        HIP_TRY(hipMemcpyAsync(energies, de.p, sizeof(double) * items, hipMemcpyDeviceToHost, stream));
+        if (probs) HIP_TRY(hipMemcpyAsync(probs, dp.p, sizeof(double) * items, hipMemcpyDeviceToHost, stream));
+        if (status) HIP_TRY(hipMemcpyAsync(status, ds.p, items, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
         return ADX_OK;
     }
 

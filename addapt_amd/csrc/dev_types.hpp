@@ -105,6 +105,26 @@ struct DevScaled {
     float motif_extra;              // exp(-Eint)(exp(-bonus)-1) * sigma^L
 };
 
+// What struct_eval_kernel (struct_eval.hip) reads besides an energy-valued
+// DevTables (the MFE image, setup_core.hpp build_tables): the loop-length
+// energies of every size and the few constants of one convention, in dcal/mol.
+// Built on the host (setup_core.hpp build_eval_tab) and uploaded, so that the
+// host's and the device's long-loop values are the same doubles.
+constexpr int EV_HP = 0, EV_BUL = 1, EV_INT = 2;
+struct EvalTab {
+    // [kind][u]: the table entry up to 30 unpaired bases; above, entry[30] +
+    // lxc ln(u / 30): as computed (PF convention) or the ln term truncated to
+    // an integer first (MFE convention, oracle/fold.c E_hairpin_int)
+    double len[3][NMAX + 1];
+    int nin[NMAX + 1];            // min(MAX_NINIO, k * ninio)
+    int sp_e[MAX_SPECIAL_HP];     // special hairpins, in DevScaled::sp_key's order
+    int mlclosing, mlbase;
+    int mfe;                      // the convention: 0 = PF, 1 = MFE
+    int m_mfe_dcal;               // MFE: a formed motif site's energy, lround(100 (eint + beff))
+    double m_eint, m_beff;        // PF: the motif's intrinsic energy and effective bonus, kcal/mol
+    double kT;                    // kcal/mol
+};
+
 struct DevVariant {
     int N;            // folded length (context-padded)
     int before_len;   // context prefix length

@@ -80,6 +80,18 @@ hipError_t launch_pf_fill(const KArgs &ka, int variant, const uint8_t *seqs, int
 hipError_t launch_pf_sample(const KArgs &ka, int variant, const uint8_t *seqs, int w0, int n, double *scratch,
                             int k0, int nk, uint64_t seed, char *structures, int *flag, hipStream_t stream);
 
+// ---- struct_eval.hip: energies, probabilities and status bytes of given structures,
+// one wave per (sequence, structure) item.  Sequences w0 .. w0 + n of `seqs`, n_per
+// structures each: structure k of sequence b at structures + b * seq_stride + k * L
+// (seq_stride 0: one list shared by every sequence), outputs at out0 + b * n_per + k.
+// TE: energy-valued tables (the MFE image), E: the convention's EvalTab.  probs
+// (optional, PF problems only) reads the totals launch_pf_fill left for these n
+// sequences in `fill`; status is optional.
+hipError_t launch_struct_eval(const KArgs &ka, const DevTables *TE, const EvalTab *E, int variant,
+                              const uint8_t *seqs, int w0, int n, int n_per, const char *structures,
+                              size_t seq_stride, const double *fill, size_t out0, double *energies, double *probs,
+                              uint8_t *status, hipStream_t stream);
+
 // ---- ensemble_struct.hip: centroid and MEA structures of n sequences from their
 // pair-probability matrices probs[n][L][L] (launch_bppm's `full`, ld = L):
 // centroid, mea = n * L chars, stats = n * 3 doubles (mea, centroid_dist, diversity)

@@ -279,6 +279,34 @@ inline void build_scaled(const EnergyParams &P, double sigma, const Motif &m, do
     }
 }
 
+// struct_eval_kernel's table (dev_types.hpp EvalTab) in the PF (mfe false) or
+// MFE convention; the motif as build_scaled reads it (AUTO: ADD in PF, REPLACE in MFE)
+inline void build_eval_tab(const EnergyParams &P, const Motif &m, double eint, EvalTab &E, bool mfe) {
+    std::memset(&E, 0, sizeof E);
+    const int *tab[3] = {P.hairpin, P.bulge, P.interior};
+    for (int kind = 0; kind < 3; kind++)
+        for (int u = 0; u <= NMAX; u++) {
+            if (u <= 30) E.len[kind][u] = tab[kind][u];
+            else if (mfe) E.len[kind][u] = tab[kind][30] + static_cast<int>(P.lxc * std::log(u / 30.0));
+            else E.len[kind][u] = tab[kind][30] + P.lxc * std::log(u / 30.0);
+        }
+    for (int k = 0; k <= NMAX; k++) E.nin[k] = std::min(P.maxninio, k * P.ninio);
+    int nsp = 0;
+    for (const auto *t : {&P.triloops, &P.tetraloops, &P.hexaloops})
+        for (const auto &e : *t)
+            if (nsp < MAX_SPECIAL_HP) E.sp_e[nsp++] = e.second;
+    E.mlclosing = P.MLclosing;
+    E.mlbase = P.MLbase;
+    E.mfe = mfe ? 1 : 0;
+    E.kT = kT_kcal();
+    if (m.present) {
+        const bool replace = m.mode == ADX_MOTIF_REPLACE || (m.mode == ADX_MOTIF_AUTO && mfe);
+        E.m_eint = eint;
+        E.m_beff = replace ? m.energy_kcal - eint : m.energy_kcal;
+        E.m_mfe_dcal = static_cast<int>(std::lround(100.0 * (eint + E.m_beff)));
+    }
+}
+
 // Dot-bracket hard constraint (DB_DEFAULT | ENFORCE_BP, scoring.cc:61-62) ->
 // five byte arrays of length N+2: up, dn, ptn, enc, flg (see fold_common.hpp allowed()).
 inline adx_status build_constraint(const std::string &cst, int N, std::vector<uint8_t> &out, SetupError &err) {

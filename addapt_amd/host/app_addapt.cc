@@ -5,6 +5,7 @@
 //                      [-i <steps>] [--walkers <W>] [--gpu <id>] [--params <file>]
 //                      [--reference-loop] [--picks <path>] [--pick-window <steps>|auto]
 //                      [--autocorr <path>] [--autocorr-lag <steps>] [--autocorr-discard <steps>]
+//                      [--eval <path> --eval-structure <db>[,<db>...]]
 //                      [--designs <path>] [--design-radius <mutations>] [--max-designs <num>]
 #include <algorithm>
 #include <cmath>
@@ -72,6 +73,15 @@ static const char USAGE[] =
     "  --design-radius <mutations>            [default: 3]\n"
     "    Leaders are more than this many mutations apart (0: exact duplicates only).\n"
     "  --max-designs <num>                    [default: 100]\n"
+    "  --eval <path>\n"
+    "    With --walkers and --eval-structure: price the target structures on every\n"
+    "    walker's final sequence on the GPU and write one row per walker, target and\n"
+    "    unconstrained (context, condition) fold of the target's length: the energy\n"
+    "    (kcal/mol), the structure's probability in that fold's ensemble and a status\n"
+    "    (0: in the ensemble; 1 malformed, 2 hairpin below 3, 4 excluded, 8 interior\n"
+    "    loop above 30, or-ed).  A '#' line gives the device time of the last call.\n"
+    "  --eval-structure <db>[,<db>...]\n"
+    "    The target structures, dot-bracket, of the (context-padded) folded length.\n"
     "  --gpu <id>                             [default: 0]\n"
     "  --params <file>  Energy parameters (ViennaRNA 2.0 format).\n"
     "  --reference-loop  Run the reference's single-walker loop (one GPU fold call\n"
@@ -152,9 +162,25 @@ static void write_designs(const std::string &path, const BatchResult &res, int r
     std::fclose(f);
 }
 
+// The target structures of a batched run priced on the final walkers.
+static void write_evals(const std::string &path, const BatchResult &res, const std::vector<std::string> &targets,
+                        const std::vector<uint32_t> &seeds) {
+    FILE *f = std::fopen(path.c_str(), "w");
+    if (!f) throw std::string("couldn't open '" + path + "' for writing");
+    std::fprintf(f, "# Num Targets: %zu\n# Last Eval ms: fill %.3f kernel %.3f\n", targets.size(), res.eval_fill_ms,
+                 res.eval_ms);
+    std::fprintf(f, "walker\tseed\ttarget\tcontext\tcondition\tenergy\tprobability\tstatus\tstructure\n");
+    for (auto &x : res.evals)
+        std::fprintf(f, "%d\t%u\t%d\t%d\t%s\t%.17g\t%.17g\t%d\t%s\n", x.walker, seeds[size_t(x.walker)], x.target,
+                     x.context, x.condition ? "holo" : "apo", x.energy, x.prob, x.status,
+                     targets[size_t(x.target)].c_str());
+    std::fclose(f);
+}
+
 int main(int argc, char **argv) {
     std::vector<std::string> configs;
-    std::string temp, out = "traj.tsv", params, picks, autocorr, designs;
+    std::string temp, out = "traj.tsv", params, picks, autocorr, designs, evals;
+    std::vector<std::string> targets;
     int num = 100, interval = 1, walkers = 1, gpu = 0, pick_window = 500, autocorr_lag = 500, autocorr_discard = 100;
     int design_radius = 3, max_designs = 100;
     bool auto_window = false;
@@ -187,6 +213,15 @@ int main(int argc, char **argv) {
             else if (a == "--designs") designs = val("--designs");
             else if (a == "--design-radius") design_radius = std::stoi(val("--design-radius"));
             else if (a == "--max-designs") max_designs = std::stoi(val("--max-designs"));
+            else if (a == "--eval") evals = val("--eval");
+            else if (a == "--eval-structure") {
+                std::string v = val("--eval-structure"), t;
+                for (char ch : v + ",") {
+                    if (ch != ',') { t.push_back(ch); continue; }
+                    if (!t.empty()) targets.push_back(t);
+                    t.clear();
+                }
+            }
             else if (a == "--gpu") gpu = std::stoi(val("--gpu"));
             else if (a == "--params") params = val("--params");
             else if (a == "--reference-loop") ref_loop = true;
@@ -199,6 +234,8 @@ int main(int argc, char **argv) {
         }
         if (!picks.empty() && walkers <= 1) throw std::string("--picks needs --walkers <W> with W > 1");
         if (!designs.empty() && walkers <= 1) throw std::string("--designs needs --walkers <W> with W > 1");
+        if (!evals.empty() && walkers <= 1) throw std::string("--eval needs --walkers <W> with W > 1");
+        if (evals.empty() != targets.empty()) throw std::string("--eval <path> and --eval-structure <db>[,<db>...] go together");
         const bool picking = !picks.empty() || !designs.empty();
         if (picking && !auto_window && pick_window < 1) throw std::string("--pick-window must be at least 1");
         if (!designs.empty() && design_radius < 0) throw std::string("--design-radius must not be negative");
@@ -228,6 +265,7 @@ int main(int argc, char **argv) {
             }
             opt.autocorr_lag = correlating ? autocorr_lag : 0;
             opt.autocorr_discard = correlating ? autocorr_discard : 0;
+            opt.eval_structures = targets;
             auto res = mc->apply_batch(device, seeds, gpu, opt);
             FILE *f = std::fopen(out.c_str(), "w");
             if (!f) throw std::string("couldn't open '" + out + "' for writing");
@@ -243,6 +281,7 @@ int main(int argc, char **argv) {
             if (!picks.empty()) write_picks(picks, res, seeds);
             if (!autocorr.empty()) write_autocorr(autocorr, res.autocorr);
             if (!designs.empty()) write_designs(designs, res, design_radius, seeds);
+            if (!evals.empty()) write_evals(evals, res, targets, seeds);
             return 0;
         }
         *mc += std::make_shared<ProgressReporter>();

@@ -272,6 +272,13 @@ BatchResult MonteCarlo::apply_batch(DevicePtr device, const std::vector<uint32_t
     if (opt.design_radius >= 0 && opt.max_designs < 1) throw string("apply_batch: max_designs must be at least 1");
     EngineSetup e;
     build_setup(*this, device, g, e);
+    // the folded length of a context's variants (no contexts: the device's own)
+    auto folded_length = [&](int c) { return e.seq.size() + (c >= 0 ? e.ctx_b[size_t(c)].size() + e.ctx_a[size_t(c)].size() : 0); };
+    for (auto &t : opt.eval_structures) {   // before the run, not after it
+        bool fits = e.ctx.empty() && t.size() == folded_length(-1);
+        for (size_t c = 0; c < e.ctx.size(); c++) fits = fits || t.size() == folded_length(int(c));
+        if (!fits) throw string("apply_batch: target structure '" + t + "' has the folded length of no context");
+    }
     adx_ctx *raw = nullptr;
     gpu::check(adx_ctx_create(&e.d, &raw));
     gpu::CtxPtr ctx(raw);
@@ -368,6 +375,36 @@ BatchResult MonteCarlo::apply_batch(DevicePtr device, const std::vector<uint32_t
             out.designs.push_back(Design{dw[d], dsteps[d], dscores[d], string(&dseqs[size_t(d) * N], N), dsz[d], dnw[d]});
     }
     if (picking || correlating) gpu::check(adx_record_end(ctx.get()));
+    if (!opt.eval_structures.empty()) {
+        adx_info info;
+        gpu::check(adx_ctx_info(ctx.get(), &info));
+        const size_t T = opt.eval_structures.size();
+        std::vector<std::vector<TargetEval>> per(size_t(W) * T);   // rows of (walker, target), folds in variant order
+        for (int v = 0; v < info.n_variants; v++) {
+            int c = -1, cond = 0, mac = -1;
+            gpu::check(adx_variant_desc(ctx.get(), v, &c, &cond, &mac));
+            if (mac >= 0) continue;   // the unconstrained folds only
+            std::vector<int> idx;
+            string all;
+            for (size_t t = 0; t < T; t++)
+                if (opt.eval_structures[t].size() == folded_length(c)) {
+                    idx.push_back(int(t));
+                    all += opt.eval_structures[t];
+                }
+            if (idx.empty()) continue;
+            const size_t n = idx.size();
+            std::vector<double> en(size_t(W) * n), pr(size_t(W) * n);
+            std::vector<uint8_t> st(size_t(W) * n);
+            gpu::check(adx_walkers_eval_structures(ctx.get(), v, int(n), all.c_str(), en.data(), pr.data(), st.data()));
+            for (int w = 0; w < W; w++)
+                for (size_t k = 0; k < n; k++) {
+                    const size_t o = size_t(w) * n + k;
+                    per[size_t(w) * T + size_t(idx[k])].push_back(TargetEval{w, idx[k], c, cond, en[o], pr[o], int(st[o])});
+                }
+        }
+        gpu::check(adx_last_eval_ms(ctx.get(), &out.eval_fill_ms, &out.eval_ms));
+        for (auto &rows : per) out.evals.insert(out.evals.end(), rows.begin(), rows.end());
+    }
     for (int w = 0; w < W; w++) {
         out[w].device = device->copy();
         for (size_t k = 0; k < N; k++) out[w].device->mutate(int(k), seqs[size_t(w) * N + k]);

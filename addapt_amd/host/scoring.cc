@@ -107,6 +107,32 @@ std::pair<std::vector<string>, double> GpuRnaFold::sample_structures(int n, uint
     return {out, double(e)};
 }
 
+// RNAeval on the fold compound macrostate_prob builds
+std::vector<StructureEval> GpuRnaFold::eval_structures(const std::vector<string> &structures, string constraint,
+                                                       bool mfe) const {
+    adx_fold *raw = nullptr;
+    gpu::check(adx_fold_create(gpu::params(), seq_.c_str(), 0, gpu_, &raw));
+    gpu::FoldPtr f(raw);
+    if (aptamer_)
+        gpu::check(adx_fold_add_motif(f.get(), aptamer_->seq().c_str(), aptamer_->fold().c_str(),
+                                      kT() * std::log(aptamer_->affinity() / 1e6)));
+    if (!constraint.empty()) gpu::check(adx_fold_add_constraint(f.get(), constraint.c_str()));
+    const size_t n = structures.size();
+    string all;
+    for (auto &s : structures) {
+        if (s.size() != seq_.size()) throw string("eval_structures: structure '" + s + "' does not have the sequence's length");
+        all += s;
+    }
+    std::vector<StructureEval> out(n);
+    if (n == 0) return out;
+    std::vector<double> e(n), p(n, std::nan(""));
+    std::vector<uint8_t> st(n);
+    gpu::check(adx_fold_eval_structures(f.get(), mfe ? ADX_FOLD_MFE : ADX_FOLD_PF, int(n), all.c_str(), e.data(),
+                                        mfe ? nullptr : p.data(), st.data()));
+    for (size_t k = 0; k < n; k++) out[k] = StructureEval{e[k], p[k], int(st[k])};
+    return out;
+}
+
 // RNAfold -p --MEA on the fold compound macrostate_prob builds
 EnsembleStructures GpuRnaFold::ensemble_structures(double gamma, string constraint) const {
     adx_fold *raw = nullptr;

@@ -85,6 +85,7 @@ EXPORTS = [
     "adx_fold_mfe_structure", "adx_mfe_structure_batch", "adx_walkers_mfe_structures",
     "adx_fold_sample_structures", "adx_sample_structures_batch", "adx_walkers_sample_structures",
     "adx_last_sample_ms",
+    "adx_fold_eval_structures", "adx_eval_structures_batch", "adx_walkers_eval_structures", "adx_last_eval_ms",
     "adx_fold_ensemble_structures", "adx_ensemble_structures_batch", "adx_walkers_ensemble_structures",
     "adx_last_ensemble_ms",
     "adx_pick_scores", "adx_record_begin", "adx_record_end", "adx_record_picks", "adx_last_pick_ms",
@@ -129,6 +130,13 @@ def lib():
         L.adx_walkers_sample_structures.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_char_p,
                                                     C.POINTER(C.c_float)]
         L.adx_last_sample_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.adx_fold_eval_structures.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_double),
+                                               C.POINTER(C.c_double), C.POINTER(C.c_uint8)]
+        L.adx_eval_structures_batch.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_char_p,
+                                                C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint8)]
+        L.adx_walkers_eval_structures.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_double),
+                                                  C.POINTER(C.c_double), C.POINTER(C.c_uint8)]
+        L.adx_last_eval_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.adx_fold_ensemble_structures.argtypes = [C.c_void_p, C.c_double, C.c_char_p, C.c_char_p,
                                                    C.POINTER(EnsembleStats)]
         L.adx_ensemble_structures_batch.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_double,
@@ -196,6 +204,27 @@ def _check(status):
 
 def _b(s):
     return s.encode() if isinstance(s, str) else s
+
+
+# status bits of the eval-structures calls (include/addapt_gpu.h ADX_EVAL_*)
+EVAL_MALFORMED, EVAL_HAIRPIN, EVAL_EXCLUDED, EVAL_BIGLOOP = 1, 2, 4, 8
+
+
+def _eval_structures(n_seqs, n_per, L, structures, with_probs, call):
+    """The three outputs of an eval-structures call as (n_seqs, n_per) arrays; probs None without with_probs."""
+    flat = [_b(s) for s in structures]
+    if any(len(s) != L for s in flat):
+        raise ValueError("every structure must have the folded length %d" % L)
+    buf = b"".join(flat)
+    n = n_seqs * n_per
+    e = np.zeros(n, np.float64)
+    p = np.zeros(n, np.float64) if with_probs else None
+    st = np.zeros(n, np.uint8)
+    _check(call(buf, e.ctypes.data_as(C.POINTER(C.c_double)),
+                p.ctypes.data_as(C.POINTER(C.c_double)) if with_probs else None,
+                st.ctypes.data_as(C.POINTER(C.c_uint8))))
+    shape = (n_seqs, n_per)
+    return e.reshape(shape), p.reshape(shape) if with_probs else None, st.reshape(shape)
 
 
 def kT():
@@ -362,6 +391,18 @@ class Fold:
         _check(lib().adx_fold_sample_structures(self.ptr, n, seed, buf, C.byref(g)))
         raw = buf.raw[:n * self.N].decode()
         return g.value, [raw[k * self.N:(k + 1) * self.N] for k in range(n)]
+
+    def eval_structures(self, structures, convention="pf", with_probs=False):
+        """(energies kcal/mol, probabilities or None, status bytes) of the given dot-bracket
+        strings on this sequence, motif and constraint honoured: RNAeval on the GPU.
+        convention "pf" (E = -kT ln of the ensemble's weight) or "mfe" (the MFE folds'
+        integer arithmetic); with_probs ("pf" only): exp(-(E - G) / kT).  status 0 = a
+        member of the ensemble, else EVAL_* bits."""
+        n = len(structures)
+        conv = {"pf": 0, "mfe": 1}[convention]
+        e, p, st = _eval_structures(1, n, self.N, structures, with_probs,
+                                    lambda s, en, pr, sb: lib().adx_fold_eval_structures(self.ptr, conv, n, s, en, pr, sb))
+        return e[0], p[0] if with_probs else None, st[0]
 
     def ensemble_structures(self, gamma=1.0):
         """(centroid, MEA structure, EnsembleStats) of the ensemble: RNAfold -p --MEA's
@@ -531,6 +572,32 @@ class Engine:
         """(fill ms, sampling ms) of the last sample_structures / walker_samples call, from HIP events."""
         a, b = C.c_double(), C.c_double()
         _check(lib().adx_last_sample_ms(self.ptr, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def eval_structures(self, seqs, variant, structures, with_probs=False):
+        """(energies, probabilities or None, status bytes), each (W, n), of structures[w][k] on
+        seqs[w] in fold variant `variant`, in the convention of the engine's fold mode
+        (with_probs: fold_mode="pf" engines).  structures: W lists of n dot-bracket strings
+        of the variant's folded length, as sample_structures returns them."""
+        W, n = len(seqs), len(structures[0]) if structures else 0
+        if len(structures) != W or any(len(row) != n for row in structures):
+            raise ValueError("structures must be one list of equal length per sequence")
+        seqbuf = b"".join(_b(s) for s in seqs)
+        return _eval_structures(W, n, self._variant_length(variant), [s for row in structures for s in row], with_probs,
+                                lambda s, e, p, st: lib().adx_eval_structures_batch(self.ptr, W, seqbuf, variant, n, s,
+                                                                                    e, p, st))
+
+    def walker_eval_structures(self, variant, structures, with_probs=False):
+        """The same (W, n) arrays for one list of n target structures on every walker's
+        current sequence, read on the device."""
+        n = len(structures)
+        return _eval_structures(max(self.W, 0), n, self._variant_length(variant), structures, with_probs,
+                                lambda s, e, p, st: lib().adx_walkers_eval_structures(self.ptr, variant, n, s, e, p, st))
+
+    def last_eval_ms(self):
+        """(fill ms, eval ms) of the last eval_structures / walker_eval_structures call, from HIP events."""
+        a, b = C.c_double(), C.c_double()
+        _check(lib().adx_last_eval_ms(self.ptr, C.byref(a), C.byref(b)))
         return a.value, b.value
 
     def _ensemble(self, W, condition, context, with_probs, call):

@@ -190,6 +190,18 @@ struct Design {
     int walkers;         ///< the distinct walkers among them: how often the design was found independently
 };
 
+/// one target structure priced on one walker's final sequence (adx_walkers_eval_structures)
+/// for one unconstrained (context, condition) fold of the score function
+struct TargetEval {
+    int walker;
+    int target;          ///< index into BatchOptions::eval_structures
+    int context;         ///< the score function's context (-1: none)
+    int condition;       ///< 0 apo, 1 holo
+    double energy;       ///< kcal/mol (NaN malformed, +inf hairpin below 3)
+    double prob;         ///< its share of that fold's ensemble; 0 for a non-member
+    int status;          ///< 0: a member, else ADX_EVAL_* bits (addapt_gpu.h)
+};
+
 /// the walkers' results; with a pick window also how often A, C, G, U stand at
 /// each position over all walkers' picks (base_counts[4 * position + base])
 struct BatchResult : std::vector<WalkerResult> {
@@ -198,6 +210,8 @@ struct BatchResult : std::vector<WalkerResult> {
     std::vector<Design> designs;       ///< filled with BatchOptions::design_radius >= 0: best leader first
     std::vector<int64_t> pair_hist;    ///< then [d], d = 0..N: the pairs of picks d mutations apart
     int64_t n_picks = 0;               ///< and the number of picks the designs were selected from
+    double eval_fill_ms = 0.0, eval_ms = 0.0;   ///< device time of the last eval call (adx_last_eval_ms): FP64 fill, kernel
+    std::vector<TargetEval> evals;     ///< filled with BatchOptions::eval_structures: walker-major, then target, then fold
 };
 
 /// what a batched run does besides stepping
@@ -210,6 +224,8 @@ struct BatchOptions {
     int design_radius = -1;     ///< >= 0: the distinct designs among the picks, leaders more than this many
                                 ///< mutations apart (needs a pick window, fixed or automatic)
     int max_designs = 100;      ///< at most this many designs
+    std::vector<std::string> eval_structures;   ///< target dot-brackets priced on every walker's final sequence, in each
+                                                ///< unconstrained (context, condition) fold of their (context-padded) length
 };
 
 class MonteCarlo {

@@ -55,6 +55,13 @@ struct EnsembleStructures {
     double diversity;       ///< the ensemble's mean base-pair distance (vrna_mean_bp_distance)
 };
 
+/// What a sequence pays for one given structure (GpuRnaFold::eval_structures).
+struct StructureEval {
+    double energy;   ///< kcal/mol; NaN when malformed, +inf for a hairpin below 3 or a structure the constraint excludes
+    double prob;     ///< exp(-(energy - G) / kT) in the ensemble, 0 for a non-member; NaN in the MFE convention
+    int status;      ///< 0: a member of the ensemble, else ADX_EVAL_* bits (addapt_gpu.h)
+};
+
 class GpuRnaFold : public RnaFold {
 public:
     explicit GpuRnaFold(DeviceConstPtr device, AptamerConstPtr aptamer = nullptr, int gpu = 0);
@@ -73,6 +80,12 @@ public:
     /// aptamer motif counts as in macrostate_prob.  Both all '.' and the statistics
     /// NaN when the constraint admits nothing.
     EnsembleStructures ensemble_structures(double gamma = 1.0, string constraint = "") const;
+    /// RNAeval on the GPU: the energy, ensemble probability and status of each given
+    /// dot-bracket on this sequence, under an optional hard constraint; the aptamer
+    /// motif counts as in macrostate_prob.  mfe: the MFE folds' integer arithmetic
+    /// (no probabilities) instead of -kT ln of the partition function's weight.
+    std::vector<StructureEval> eval_structures(const std::vector<string> &structures, string constraint = "",
+                                               bool mfe = false) const;
 
 private:
     string seq_;

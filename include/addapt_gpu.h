@@ -98,6 +98,37 @@ adx_status adx_fold_mfe_structure(adx_fold *f, char *structure, float *energy_kc
  * admits no structure.  Filled (FP64) and sampled on the GPU. */
 adx_status adx_fold_sample_structures(adx_fold *f, int n_samples, uint64_t seed,
                                       char *structures, float *energy_kcal);
+/* RNAeval on the GPU: what the compound's sequence pays for each of n given
+ * structures, and how much of its ensemble each is.  structures = n *
+ * strlen(seq) chars, no terminators; energies[n] (kcal/mol), probs[n] and
+ * status[n] (both optional, NULL).  The compound's motif and constraint are
+ * honoured.  convention:
+ *   ADX_FOLD_PF   E(s) = -kT ln w(s), w the weight adx_fold_pf's ensemble gives s:
+ *                 adx_eval_structure's loops, and per formed motif site (the
+ *                 sequence matches, s has the motif's own fold there, the
+ *                 constraint admits it) exp(-enc/kT), enc the loops the site
+ *                 encloses, replaced by exp(-enc/kT) + exp(-eint/kT)(exp(-beff/kT) - 1)
+ *   ADX_FOLD_MFE  the integer dcal arithmetic of adx_fold_mfe: lxc ln(u/30) of a
+ *                 loop above 30 truncated, a formed site's enclosed energy
+ *                 min(enc, round(100 (eint + beff))), eint the motif's own loops,
+ *                 beff = bonus under ADX_MOTIF_ADD and bonus - eint under
+ *                 ADX_MOTIF_REPLACE and ADX_MOTIF_AUTO (so round(100 bonus) there);
+ *                 in the PF convention beff = bonus under ADD and AUTO
+ * status bits per item: ADX_EVAL_MALFORMED (unbalanced, a character outside
+ * ".()", a non-canonical pair; energy NaN), ADX_EVAL_HAIRPIN (a hairpin below 3;
+ * +inf), ADX_EVAL_EXCLUDED (the constraint excludes it; +inf), ADX_EVAL_BIGLOOP
+ * (an interior loop above 30: priced as adx_eval_structure prices it, yet in no
+ * fold's ensemble).  status 0 = a member of the ensemble; a string without a
+ * pair table (unbalanced, a bad character) reports ADX_EVAL_MALFORMED alone.
+ * A bad item never disturbs its neighbours.  probs (ADX_FOLD_PF
+ * only): exp(-(E(s) - G)/kT) with G from an FP64 fill on the GPU, 0 for a
+ * non-member. */
+#define ADX_EVAL_MALFORMED 1
+#define ADX_EVAL_HAIRPIN 2
+#define ADX_EVAL_EXCLUDED 4
+#define ADX_EVAL_BIGLOOP 8
+adx_status adx_fold_eval_structures(adx_fold *f, int convention, int n, const char *structures,
+                                    double *energies, double *probs, uint8_t *status);
 /* What RNAfold -p --MEA prints after the MFE line, for the ensemble the compound
  * describes (motif, constraint), from its pair probabilities P on the GPU:
  *   centroid       the pairs with P > 1/2 (taken in ascending (i, j); a pair that
@@ -361,6 +392,29 @@ adx_status adx_walkers_ensemble_structures(adx_ctx *ctx, int condition, int cont
 /* Device time (ms, HIP events) of the context's last ensemble-structures call:
  * the outside pass and the structure kernel. */
 adx_status adx_last_ensemble_ms(const adx_ctx *ctx, double *bppm_ms, double *struct_ms);
+
+/* Energies, ensemble probabilities and status bytes (adx_fold_eval_structures)
+ * of given structures for variant v (adx_variant_desc), in the convention of
+ * the context's fold mode and with the variant's context padding, constraint
+ * and motif: n_seqs sequences (n_seqs*N chars), n_per_seq structures each.
+ * structures = n_seqs * n_per_seq * L chars (sequence-major; L = the variant's
+ * folded, context-padded length), the layout adx_sample_structures_batch writes
+ * and, with n_per_seq = 1, adx_mfe_structure_batch's.  energies, probs and
+ * status are n_seqs * n_per_seq, sequence-major; probs and status optional
+ * (NULL); probs on an MFE context: ADX_EUNSUPPORTED.  Walker state, the stored
+ * tables and the next step's results are not touched. */
+adx_status adx_eval_structures_batch(adx_ctx *ctx, int n_seqs, const char *seqs, int variant, int n_per_seq,
+                                     const char *structures, double *energies, double *probs, uint8_t *status);
+
+/* n_structs target structures (n_structs * L chars, shared by all walkers) on
+ * the walkers' current sequences, read on the device: outputs are W * n_structs,
+ * walker-major (ADX_ESTATE before adx_walkers_init). */
+adx_status adx_walkers_eval_structures(adx_ctx *ctx, int variant, int n_structs, const char *structures,
+                                       double *energies, double *probs, uint8_t *status);
+
+/* Device time (ms, HIP events) of the context's last eval-structures call: the
+ * FP64 fill (0 without probs) and the eval kernel. */
+adx_status adx_last_eval_ms(const adx_ctx *ctx, double *fill_ms, double *eval_ms);
 
 /* ------------------------------------------------------------------------
  * Picking each trajectory's best steps on the device (what the reference's
