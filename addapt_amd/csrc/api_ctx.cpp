@@ -644,6 +644,53 @@ extern "C" adx_status adx_walkers_mfe_structures(adx_ctx *c, int variant, char *
     return mfe_structures(c, "adx_walkers_mfe_structures", c->cur_seq.p, c->W, variant, structures, energies);
 }
 
+// Zuker suboptimal structures of W device sequences for variant v, copied to the host
+static adx_status subopt_structures(adx_ctx *c, const char *who, const uint8_t *dseqs, int W, int v, double delta_kcal,
+                                    int max_structs, const SuboptOut &h) {
+    Problem &pb = c->pb;
+    if (pb.mode != ADX_FOLD_MFE)
+        return fail(ADX_EUNSUPPORTED, "%s: ADX_FOLD_MFE contexts only (a partition-function context holds no "
+                    "energies; use adx_fold_subopt_structures)", who);
+    if (v < 0 || v >= static_cast<int>(pb.variants.size()))
+        return fail(ADX_EINVAL, "%s: variant %d outside [0, %zu)", who, v, pb.variants.size());
+    if (!subopt_args_ok(delta_kcal, max_structs))
+        return fail(ADX_EINVAL, "%s: delta %g < 0 or max_structs %d < 1", who, delta_kcal, max_structs);
+    const size_t L = size_t(pb.variants[v].N);
+    if (size_t(W) > SIZE_MAX / L / std::max(L, size_t(max_structs)) / sizeof(float))
+        return fail(ADX_EINVAL, "%s: %d x %d structures of %zu chars overflow", who, W, max_structs, L);
+    return pb.subopt(dseqs, W, v, delta_kcal, max_structs, h);
+}
+
+extern "C" adx_status adx_subopt_structures_batch(adx_ctx *c, int W, const char *seqs, int variant, double delta_kcal,
+                                                  int max_structs, int *n_found, int *n_pairs_within, float *mfe_kcal,
+                                                  char *structures, float *energies, int *seeds, float *pair_energy) {
+    if (!c || W <= 0 || !seqs || !n_found || !mfe_kcal || !structures || !energies)
+        return fail(ADX_EINVAL, "adx_subopt_structures_batch: bad argument");
+    Problem &pb = c->pb;
+    DevBuf<uint8_t> dseq;
+    if (adx_status su = upload_codes(seqs, size_t(W) * pb.Nraw, dseq, pb.stream)) return su;
+    return subopt_structures(c, "adx_subopt_structures_batch", dseq.p, W, variant, delta_kcal, max_structs,
+                             SuboptOut{n_found, n_pairs_within, mfe_kcal, structures, energies, seeds, pair_energy});
+}
+
+extern "C" adx_status adx_walkers_subopt_structures(adx_ctx *c, int variant, double delta_kcal, int max_structs,
+                                                    int *n_found, int *n_pairs_within, float *mfe_kcal,
+                                                    char *structures, float *energies, int *seeds, float *pair_energy) {
+    if (!c || !n_found || !mfe_kcal || !structures || !energies)
+        return fail(ADX_EINVAL, "adx_walkers_subopt_structures: null argument");
+    if (c->pb.mode == ADX_FOLD_MFE && c->W <= 0)
+        return fail(ADX_ESTATE, "adx_walkers_subopt_structures before adx_walkers_init");
+    return subopt_structures(c, "adx_walkers_subopt_structures", c->cur_seq.p, c->W, variant, delta_kcal, max_structs,
+                             SuboptOut{n_found, n_pairs_within, mfe_kcal, structures, energies, seeds, pair_energy});
+}
+
+extern "C" adx_status adx_last_subopt_ms(const adx_ctx *c, double *fill_ms, double *select_ms) {
+    if (!c || !fill_ms || !select_ms) return fail(ADX_EINVAL, "adx_last_subopt_ms: null argument");
+    *fill_ms = c->pb.subopt_fill_ms;
+    *select_ms = c->pb.subopt_select_ms;
+    return ADX_OK;
+}
+
 // n_samples structures per device sequence for variant v, drawn from its ensemble
 static adx_status sample_structures(adx_ctx *c, const char *who, const uint8_t *dseqs, int W, int v, int n_samples,
                                     uint64_t seed, char *structures, float *energies) {

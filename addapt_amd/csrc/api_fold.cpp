@@ -196,6 +196,31 @@ extern "C" adx_status adx_fold_mfe_structure(adx_fold *f, char *structure, float
     return ADX_OK;
 }
 
+extern "C" adx_status adx_fold_subopt_structures(adx_fold *f, double delta_kcal, int max_structs, int *n_found,
+                                                 int *n_pairs_within, float *mfe_kcal, char *structures,
+                                                 float *energies, int *seeds, float *pair_energy) {
+    if (!f || !n_found || !mfe_kcal || !structures || !energies)
+        return fail(ADX_EINVAL, "adx_fold_subopt_structures: null argument");
+    if (!subopt_args_ok(delta_kcal, max_structs))
+        return fail(ADX_EINVAL, "adx_fold_subopt_structures: delta %g < 0 or max_structs %d < 1", delta_kcal, max_structs);
+    Problem pb;
+    adx_status s = fold_problem(f, 1, pb);
+    if (s) return s;
+    const size_t N = f->seq.size();
+    DevBuf<uint8_t> dseq;
+    s = upload_codes(f->seq.data(), N, dseq, pb.stream);
+    if (s) return s;
+    std::vector<char> rows(size_t(max_structs) * N);
+    s = pb.subopt(dseq.p, 1, 0, delta_kcal, max_structs,
+                  SuboptOut{n_found, n_pairs_within, mfe_kcal, rows.data(), energies, seeds, pair_energy});
+    if (s) return s;
+    for (int k = 0; k < max_structs; k++) {   // NUL-terminated rows
+        std::memcpy(structures + size_t(k) * (N + 1), rows.data() + size_t(k) * N, N);
+        structures[size_t(k) * (N + 1) + N] = 0;
+    }
+    return ADX_OK;
+}
+
 extern "C" adx_status adx_fold_sample_structures(adx_fold *f, int n_samples, uint64_t seed, char *structures,
                                                  float *energy) {
     if (!f || !structures) return fail(ADX_EINVAL, "adx_fold_sample_structures: null argument");

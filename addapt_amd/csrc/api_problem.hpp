@@ -61,6 +61,8 @@ struct Problem : DeviceStream {
     DevBuf<uint8_t> dCls;        // the folds' weight classes (KArgs::ocls, the proposals' or a rescore's)
     DevBuf<int> dPairQ;          // mfe_pair_kernel's work queue (KArgs::pairq)
     DevBuf<int> dTrace;          // c / fm / fm1 scratch of mfe_trace_kernel, one launch chunk
+    DevBuf<int> dSubopt;         // the seven triangles, f5 and f3 of mfe_subopt_kernel, one launch chunk
+    float subopt_fill_ms = 0.f, subopt_select_ms = 0.f;   // the last subopt() call, from HIP events
     DevBuf<double> dSample;      // qb / qm / qm1 / q5 scratch of pf_fill_kernel, one launch chunk
     float sample_fill_ms = 0.f, sample_draw_ms = 0.f;   // the last sample() call, from HIP events
     float ens_bppm_ms = 0.f, ens_struct_ms = 0.f;       // the last ensemble() call, from HIP events
@@ -264,6 +266,60 @@ struct Problem : DeviceStream {
         const size_t need = size_t(chunk) * mfe_trace_slice_ints(ka);
         if (dTrace.n < need) HIP_TRY(dTrace.alloc(need));
         HIP_TRY(launch_mfe_trace(ka, v, dseqs, W, dTrace.p, chunk, dstruct, denergy, stream));
+        return ADX_OK;
+    }
+
+    // Zuker suboptimal structures of W sequences (device codes) for one variant, to the
+    // HOST buffers of h (launch.hpp SuboptOut's layout; n_within, seeds and pair_energy
+    // optional).  mfe_subopt.hip: per launch chunk the fill phase, then the selection
+    // phase on the same scratch slices; touches no fold state.
+    // ADX_SUBOPT_CHUNK=<n> (tests) bounds the sequences per launch; the results do not depend on it.
+    adx_status subopt(const uint8_t *dseqs, int W, int v, double delta_kcal, int max_structs, const SuboptOut &h) {
+        const KArgs ka = kargs();
+        const size_t L = size_t(variants[v].N), K = size_t(max_structs);
+        const int delta_dcal = int(std::lround(100.0 * std::min(delta_kcal, 1.0e6)));   // 1e8 dcal: every pair
+        int chunk = mfe_subopt_chunk(ka, W);
+        if (const char *env = std::getenv("ADX_SUBOPT_CHUNK"))
+            if (std::atoi(env) > 0) chunk = std::min(chunk, std::atoi(env));
+        const size_t need = size_t(chunk) * mfe_subopt_slice_ints(ka);
+        if (dSubopt.n < need) HIP_TRY(dSubopt.alloc(need));
+        DevBuf<int> dnf, dnw, dsd;
+        DevBuf<float> dmfe, de, dpe;
+        DevBuf<char> dst;
+        HIP_TRY(dnf.alloc(W));
+        HIP_TRY(dnw.alloc(W));
+        HIP_TRY(dmfe.alloc(W));
+        HIP_TRY(dst.alloc(size_t(W) * K * L));
+        HIP_TRY(de.alloc(size_t(W) * K));
+        HIP_TRY(dsd.alloc(size_t(W) * K * 2));
+        if (h.pair_energy) HIP_TRY(dpe.alloc(size_t(W) * L * L));
+        const SuboptOut d{dnf.p, dnw.p, dmfe.p, dst.p, de.p, dsd.p, h.pair_energy ? dpe.p : nullptr};
+        Events ev;
+        if (adx_status se = ev.create(3)) return se;
+        subopt_fill_ms = subopt_select_ms = 0.f;
+        for (int w0 = 0; w0 < W; w0 += chunk) {
+            const int n = std::min(chunk, W - w0);
+            HIP_TRY(hipEventRecord(ev[0], stream));
+            HIP_TRY(launch_mfe_subopt(ka, v, dseqs, w0, n, dSubopt.p, 0, delta_dcal, max_structs, d, stream));
+            HIP_TRY(hipEventRecord(ev[1], stream));
+            HIP_TRY(launch_mfe_subopt(ka, v, dseqs, w0, n, dSubopt.p, 1, delta_dcal, max_structs, d, stream));
+            HIP_TRY(hipEventRecord(ev[2], stream));
+            HIP_TRY(hipStreamSynchronize(stream));   // the events are recorded again by the next chunk
+            float a = 0.f, b = 0.f;
+            HIP_TRY(hipEventElapsedTime(&a, ev[0], ev[1]));
+            HIP_TRY(hipEventElapsedTime(&b, ev[1], ev[2]));
+            subopt_fill_ms += a;
+            subopt_select_ms += b;
+        }
+        HIP_TRY(hipMemcpyAsync(h.n_found, dnf.p, sizeof(int) * W, hipMemcpyDeviceToHost, stream));
+        if (h.n_within) HIP_TRY(hipMemcpyAsync(h.n_within, dnw.p, sizeof(int) * W, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipMemcpyAsync(h.mfe, dmfe.p, sizeof(float) * W, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipMemcpyAsync(h.structures, dst.p, size_t(W) * K * L, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipMemcpyAsync(h.energies, de.p, sizeof(float) * W * K, hipMemcpyDeviceToHost, stream));
+        if (h.seeds) HIP_TRY(hipMemcpyAsync(h.seeds, dsd.p, sizeof(int) * W * K * 2, hipMemcpyDeviceToHost, stream));
+        if (h.pair_energy)
+            HIP_TRY(hipMemcpyAsync(h.pair_energy, dpe.p, sizeof(float) * W * L * L, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
         return ADX_OK;
     }
 
@@ -506,6 +562,8 @@ inline adx_status calibrate(Problem &pb, const std::vector<uint8_t> &codes) {
     }
     return fail(ADX_EINVAL, "could not find a partition-function scale for this sequence");
 }
+
+inline bool subopt_args_ok(double delta_kcal, int max_structs) { return delta_kcal >= 0.0 && max_structs >= 1; }   // NaN: no
 
 inline bool ensemble_args_ok(double gamma, const char *centroid, const char *mea, const adx_ensemble_stats *stats) {
     return std::isfinite(gamma) && gamma > 0.0 && (centroid || mea || stats);

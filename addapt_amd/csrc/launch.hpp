@@ -67,6 +67,24 @@ int mfe_trace_chunk(const KArgs &ka, int W);    // sequences per launch, so the 
 hipError_t launch_mfe_trace(const KArgs &ka, int variant, const uint8_t *seqs, int W, int *scratch, int chunk,
                             char *structures, float *energies, hipStream_t stream);
 
+// ---- mfe_subopt.hip: Zuker suboptimal structures (inside + outside MFE fill, then
+// selection and traceback; one workgroup per sequence).  Sequences w0 .. w0 + n of
+// `seqs`; phase 0 fills the scratch slices and writes mfe, n_within and (optional)
+// pair_energy, phase 1 reads the same slices and writes the list.  Outputs are
+// device buffers indexed by the sequence's position in `seqs`.
+struct SuboptOut {
+    int *n_found, *n_within;   // [W]
+    float *mfe;                // [W] kcal/mol, +inf: the constraint admits nothing
+    char *structures;          // [W][max_structs][L], '.' beyond n_found
+    float *energies;           // [W][max_structs], +inf beyond n_found
+    int *seeds;                // [W][max_structs][2], 1-based, 0 beyond n_found
+    float *pair_energy;        // [W][L][L] kcal/mol, +inf where no structure holds the pair (optional)
+};
+size_t mfe_subopt_slice_ints(const KArgs &ka);   // ints of HBM scratch per workgroup
+int mfe_subopt_chunk(const KArgs &ka, int W);    // sequences per launch, so the scratch stays bounded
+hipError_t launch_mfe_subopt(const KArgs &ka, int variant, const uint8_t *seqs, int w0, int n, int *scratch, int phase,
+                             int delta_dcal, int max_structs, const SuboptOut &out, hipStream_t stream);
+
 // ---- pf_sample.hip: structures drawn from the ensemble (FP64 fill of n sequences
 // from w0 into `scratch`, then one wave per sample: samples [k0, k0 + nk) of each,
 // structures[n][nk][variant length]; *flag is raised by a sample that met a loop bound)

@@ -89,6 +89,32 @@ std::pair<string, double> GpuRnaFold::mfe_structure(string constraint) const {
     return {structure, double(e)};
 }
 
+// RNAsubopt --zuker on the fold compound macrostate_prob builds
+SuboptStructures GpuRnaFold::subopt_structures(double delta, int max_structs, string constraint) const {
+    adx_fold *raw = nullptr;
+    gpu::check(adx_fold_create(gpu::params(), seq_.c_str(), 0, gpu_, &raw));
+    gpu::FoldPtr f(raw);
+    if (aptamer_)
+        gpu::check(adx_fold_add_motif(f.get(), aptamer_->seq().c_str(), aptamer_->fold().c_str(),
+                                      kT() * std::log(aptamer_->affinity() / 1e6)));
+    if (!constraint.empty()) gpu::check(adx_fold_add_constraint(f.get(), constraint.c_str()));
+    const size_t L = seq_.size(), K = size_t(max_structs > 0 ? max_structs : 0);
+    string all(K * (L + 1) + 1, '\0');
+    std::vector<float> e(K + 1);
+    std::vector<int> seeds(2 * K + 2);
+    int n_found = 0, within = 0;
+    float mfe = 0.f;
+    gpu::check(adx_fold_subopt_structures(f.get(), delta, max_structs, &n_found, &within, &mfe, &all[0], e.data(),
+                                          seeds.data(), nullptr));
+    SuboptStructures out{double(mfe), within, {}, {}, {}};
+    for (int k = 0; k < n_found; k++) {
+        out.structures.push_back(all.substr(size_t(k) * (L + 1), L));
+        out.energies.push_back(double(e[k]));
+        out.seeds.push_back({seeds[2 * k], seeds[2 * k + 1]});
+    }
+    return out;
+}
+
 // vrna_pbacktrack on the fold compound macrostate_prob builds
 std::pair<std::vector<string>, double> GpuRnaFold::sample_structures(int n, uint64_t seed, string constraint) const {
     adx_fold *raw = nullptr;

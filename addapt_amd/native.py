@@ -4,6 +4,7 @@ This is the Python face of the product: it loads the in-tree
 ``addapt_amd/_lib/libaddapt_gpu.so`` (built by ``__graft_entry__.build()``)
 and fails loudly when it is missing -- there is no CPU fallback.
 """
+import collections
 import ctypes as C
 import math
 import os
@@ -83,6 +84,7 @@ EXPORTS = [
     "adx_walkers_import", "adx_walkers_import_after", "adx_walkers_export_on", "adx_set_temperature", "adx_bppm_batch",
     "adx_walkers_rescore",
     "adx_fold_mfe_structure", "adx_mfe_structure_batch", "adx_walkers_mfe_structures",
+    "adx_fold_subopt_structures", "adx_subopt_structures_batch", "adx_walkers_subopt_structures", "adx_last_subopt_ms",
     "adx_fold_sample_structures", "adx_sample_structures_batch", "adx_walkers_sample_structures",
     "adx_last_sample_ms",
     "adx_fold_eval_structures", "adx_eval_structures_batch", "adx_walkers_eval_structures", "adx_last_eval_ms",
@@ -124,6 +126,12 @@ def lib():
         L.adx_mfe_structure_batch.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_int, C.c_char_p,
                                               C.POINTER(C.c_float)]
         L.adx_walkers_mfe_structures.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.POINTER(C.c_float)]
+        subopt_out = [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_float), C.c_char_p, C.POINTER(C.c_float),
+                      C.POINTER(C.c_int), C.POINTER(C.c_float)]
+        L.adx_fold_subopt_structures.argtypes = [C.c_void_p, C.c_double, C.c_int] + subopt_out
+        L.adx_subopt_structures_batch.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_int, C.c_double, C.c_int] + subopt_out
+        L.adx_walkers_subopt_structures.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_int] + subopt_out
+        L.adx_last_subopt_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.adx_fold_sample_structures.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_char_p, C.POINTER(C.c_float)]
         L.adx_sample_structures_batch.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_uint64,
                                                   C.c_char_p, C.POINTER(C.c_float)]
@@ -341,6 +349,36 @@ class Params:
         return e.value
 
 
+Subopt = collections.namedtuple("Subopt", "mfe n_pairs_within structures energies seeds pair_energy")
+
+
+def _subopt(W, L, K, with_pair_energy, call, row=None):
+    """One Subopt per sequence from a *_subopt_structures call: mfe (kcal/mol, +inf when the
+    constraint admits nothing), the number of pairs within delta, the n_found structures,
+    their float32 energies and 1-based seed pairs, and (on request) the (L, L) float32
+    energies of the best structure through every pair (+inf: none).  row: bytes per
+    structure in the call's buffer (the fold layer terminates each)."""
+    row = row or L
+    K = max(K, 0)
+    nf, nw = np.zeros(W, np.int32), np.zeros(W, np.int32)
+    mfe, e = np.zeros(W, np.float32), np.zeros(W * K, np.float32)
+    seeds = np.zeros(W * K * 2, np.int32)
+    pe = np.zeros(W * L * L if with_pair_energy else 0, np.float32)
+    buf = C.create_string_buffer(W * K * row + 1)
+    fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int)
+    _check(call(nf.ctypes.data_as(ip), nw.ctypes.data_as(ip), mfe.ctypes.data_as(fp), buf, e.ctypes.data_as(fp),
+                seeds.ctypes.data_as(ip), pe.ctypes.data_as(fp) if with_pair_energy else None))
+    raw = buf.raw
+    out = []
+    for w in range(W):
+        n = int(nf[w])
+        sts = [raw[(w * K + k) * row:(w * K + k) * row + L].decode() for k in range(n)]
+        out.append(Subopt(float(mfe[w]), int(nw[w]), sts, e[w * K:w * K + n].copy(),
+                          [tuple(int(x) for x in seeds[2 * (w * K + k):2 * (w * K + k) + 2]) for k in range(n)],
+                          pe[w * L * L:(w + 1) * L * L].reshape(L, L).copy() if with_pair_energy else None))
+    return out
+
+
 _params = None
 
 
@@ -383,6 +421,13 @@ class Fold:
         buf = C.create_string_buffer(self.N + 1)
         _check(lib().adx_fold_mfe_structure(self.ptr, buf, C.byref(g)))
         return g.value, buf.value.decode()
+
+    def subopt_structures(self, delta=3.0, max_structs=32, with_pair_energy=False):
+        """Zuker suboptimal structures (RNAsubopt --zuker): a Subopt of the structures
+        within `delta` kcal/mol of the MFE, at most one per base pair and `max_structs`
+        in all, motif and constraint honoured."""
+        return _subopt(1, self.N, max_structs, with_pair_energy,
+                       lambda *out: lib().adx_fold_subopt_structures(self.ptr, delta, max_structs, *out), self.N + 1)[0]
 
     def sample_structures(self, n, seed=0):
         """(ensemble energy kcal/mol, n dot-bracket strings drawn from the ensemble)."""
@@ -544,6 +589,26 @@ class Engine:
         """The same for the walkers' current sequences."""
         return self._structures(self.W, self._variant_length(variant), lambda st, e: lib().adx_walkers_mfe_structures(
             self.ptr, variant, st, e))
+
+    def subopt_structures(self, seqs, variant, delta=3.0, max_structs=32, with_pair_energy=False):
+        """One Subopt per sequence: the Zuker suboptimal structures of `seqs` in fold
+        variant `variant` within `delta` kcal/mol of each MFE (fold_mode="mfe" engines)."""
+        W = len(seqs)
+        seqbuf = b"".join(_b(s) for s in seqs)
+        return _subopt(W, self._variant_length(variant), max_structs, with_pair_energy,
+                       lambda *out: lib().adx_subopt_structures_batch(self.ptr, W, seqbuf, variant, delta, max_structs,
+                                                                      *out))
+
+    def walker_subopt_structures(self, variant, delta=3.0, max_structs=32, with_pair_energy=False):
+        """The same for the walkers' current sequences."""
+        return _subopt(max(self.W, 0), self._variant_length(variant), max_structs, with_pair_energy,
+                       lambda *out: lib().adx_walkers_subopt_structures(self.ptr, variant, delta, max_structs, *out))
+
+    def last_subopt_ms(self):
+        """(fill ms, selection ms) of the last subopt_structures / walker_subopt_structures call, from HIP events."""
+        a, b = C.c_double(), C.c_double()
+        _check(lib().adx_last_subopt_ms(self.ptr, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def _samples(self, W, L, n, call):
         buf = C.create_string_buffer(W * max(0, n) * L + 1)

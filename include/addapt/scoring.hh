@@ -62,6 +62,15 @@ struct StructureEval {
     int status;      ///< 0: a member of the ensemble, else ADX_EVAL_* bits (addapt_gpu.h)
 };
 
+/// Zuker suboptimal structures of one sequence (GpuRnaFold::subopt_structures).
+struct SuboptStructures {
+    double mfe;                              ///< kcal/mol; +inf when the constraint admits nothing
+    int n_pairs_within;                      ///< pairs whose best structure lies within delta of the MFE
+    std::vector<string> structures;          ///< the listed structures, energies non-decreasing
+    std::vector<double> energies;            ///< kcal/mol
+    std::vector<std::pair<int, int>> seeds;  ///< the pair each was chosen through, 1-based
+};
+
 class GpuRnaFold : public RnaFold {
 public:
     explicit GpuRnaFold(DeviceConstPtr device, AptamerConstPtr aptamer = nullptr, int gpu = 0);
@@ -71,6 +80,10 @@ public:
     /// kcal/mol, under an optional hard constraint; the aptamer motif counts as
     /// in macrostate_prob.  All '.' and +inf when the constraint admits nothing.
     std::pair<string, double> mfe_structure(string constraint = "") const;
+    /// RNAsubopt --zuker: the structures within delta kcal/mol of the MFE, at most one
+    /// per base pair and max_structs in all, under an optional hard constraint; the
+    /// aptamer motif counts as in macrostate_prob.  An MFE outside pass on the GPU.
+    SuboptStructures subopt_structures(double delta = 3.0, int max_structs = 32, string constraint = "") const;
     /// n structures drawn from the Boltzmann ensemble (vrna_pbacktrack) under an
     /// optional hard constraint, and the ensemble energy in kcal/mol; the aptamer
     /// motif counts as in macrostate_prob.  Sample k under `seed` does not depend on n.

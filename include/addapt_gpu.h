@@ -90,6 +90,28 @@ adx_status adx_fold_mfe(adx_fold *f, float *energy_kcal);
  * ligand motif appears as the motif's own fold); all '.' and +inf when the
  * constraint admits no structure.  Filled and traced on the GPU. */
 adx_status adx_fold_mfe_structure(adx_fold *f, char *structure, float *energy_kcal);
+/* RNAsubopt --zuker / mfold's energy dot plot: the structures within delta_kcal
+ * of the minimum, at most one per base pair, for the compound (motif,
+ * constraint).  An MFE outside pass on the GPU gives through(i,j), the energy of
+ * the best structure that holds the pair (i,j) -- the MFE under that forced pair
+ * -- for every pair at once.  Pairs are ordered by (through, i, j) ascending;
+ * repeatedly the first pair that no listed structure holds yet and whose
+ * through <= MFE + round(100 delta) dcal seeds the next structure (the optimal
+ * one through it, ties broken in a fixed order), until max_structs are listed or
+ * no pair is left.  The open chain is never listed.  Outputs:
+ *   n_found         structures listed
+ *   n_pairs_within  pairs with through <= MFE + delta (optional)
+ *   mfe_kcal        the minimum (+inf and n_found 0 when the constraint admits nothing)
+ *   structures      max_structs * (strlen(seq) + 1) bytes, each NUL-terminated;
+ *                   all '.' beyond n_found
+ *   energies        [max_structs] kcal/mol, non-decreasing; +inf beyond n_found
+ *   seeds           [max_structs][2] the seeding pair, 1-based; 0 beyond n_found (optional)
+ *   pair_energy     [L * L] through as float kcal/mol, symmetric, +inf where no
+ *                   structure holds the pair (optional, NULL)
+ * delta_kcal < 0 (or not finite) or max_structs < 1: ADX_EINVAL. */
+adx_status adx_fold_subopt_structures(adx_fold *f, double delta_kcal, int max_structs, int *n_found,
+                                      int *n_pairs_within, float *mfe_kcal, char *structures, float *energies,
+                                      int *seeds, float *pair_energy);
 /* vrna_pbacktrack: n_samples structures drawn from the ensemble the compound
  * describes (motif, constraint).  structures = n_samples * strlen(seq) chars,
  * no terminators; energy_kcal optional (the ensemble energy, as adx_fold_pf).
@@ -351,6 +373,30 @@ adx_status adx_mfe_structure_batch(adx_ctx *ctx, int n_walkers, const char *seqs
 /* The same for the walkers' current sequences, read on the device
  * (ADX_ESTATE before adx_walkers_init). */
 adx_status adx_walkers_mfe_structures(adx_ctx *ctx, int variant, char *structures, float *energies);
+
+/* Zuker suboptimal structures (adx_fold_subopt_structures) of W sequences (W*N
+ * chars) for variant v (adx_variant_desc), with the variant's context padding,
+ * constraint and motif.  Per sequence w: n_found[w], n_pairs_within[w]
+ * (optional), mfe_kcal[w], structures = W * max_structs * L chars (L = the
+ * variant's folded length; no terminators), energies = W * max_structs, seeds =
+ * W * max_structs * 2 (optional), pair_energy = W * L * L floats (optional, NULL).
+ * The results of a sequence depend on nothing else.  ADX_FOLD_MFE contexts only
+ * (ADX_EUNSUPPORTED on a partition-function context; use
+ * adx_fold_subopt_structures there).  Walker state, the stored tables and the
+ * next step's results are not touched. */
+adx_status adx_subopt_structures_batch(adx_ctx *ctx, int n_walkers, const char *seqs, int variant, double delta_kcal,
+                                       int max_structs, int *n_found, int *n_pairs_within, float *mfe_kcal,
+                                       char *structures, float *energies, int *seeds, float *pair_energy);
+
+/* The same for the walkers' current sequences, read on the device
+ * (ADX_ESTATE before adx_walkers_init). */
+adx_status adx_walkers_subopt_structures(adx_ctx *ctx, int variant, double delta_kcal, int max_structs, int *n_found,
+                                         int *n_pairs_within, float *mfe_kcal, char *structures, float *energies,
+                                         int *seeds, float *pair_energy);
+
+/* Device time (ms, HIP events) of the context's last suboptimal-structures call:
+ * the inside + outside fill and the selection with its tracebacks. */
+adx_status adx_last_subopt_ms(const adx_ctx *ctx, double *fill_ms, double *select_ms);
 
 /* W sequences, variant v of a PF context: structures = W * n_samples * L chars
  * (sequence-major, then sample; L = the variant's folded, context-padded
