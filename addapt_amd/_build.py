@@ -18,7 +18,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
 # the one list of the engine's sources (tools/build_variant.py builds from it too)
-GPU_SOURCES = ["fold_rows.hip", "mc_step.hip", "dispatch.hip", "mfe_cells.hip", "mfe_pair.hip", "mfe_trace.hip", "mfe_subopt.hip", "pf_sample.hip", "struct_eval.hip", "ensemble_struct.hip", "traj_pick.hip", "traj_autocorr.hip", "design_select.hip", "outside_cells.hip",
+GPU_SOURCES = ["fold_rows.hip", "mc_step.hip", "dispatch.hip", "mfe_cells.hip", "mfe_pair.hip", "mfe_trace.hip", "mfe_subopt.hip", "pf_sample.hip", "pf_access.hip", "struct_eval.hip", "ensemble_struct.hip", "traj_pick.hip", "traj_autocorr.hip", "design_select.hip", "outside_cells.hip",
                "pf_cells.hip", "pf_ring.hip", "outside_ring.hip", "api_base.cpp", "api_fold.cpp", "api_ctx.cpp", "api_record.cpp", "energy.cpp"]
 GPU_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 

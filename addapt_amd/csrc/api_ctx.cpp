@@ -777,6 +777,56 @@ extern "C" adx_status adx_last_eval_ms(const adx_ctx *c, double *fill_ms, double
     return ADX_OK;
 }
 
+// unpaired-region probabilities of W device sequences for variant v
+static adx_status unpaired_probs(adx_ctx *c, const char *who, const uint8_t *dseqs, int W, int v, int max_len,
+                                 int n_regions, const int *regions, double *profile, double *region_probs,
+                                 float *energies) {
+    Problem &pb = c->pb;
+    if (pb.mode != ADX_FOLD_PF)
+        return fail(ADX_EUNSUPPORTED, "%s: ADX_FOLD_PF contexts only (an MFE context holds no Boltzmann "
+                    "factors; use adx_fold_unpaired_probs)", who);
+    if (v < 0 || v >= static_cast<int>(pb.variants.size()))
+        return fail(ADX_EINVAL, "%s: variant %d outside [0, %zu)", who, v, pb.variants.size());
+    if (!profile && !region_probs) return fail(ADX_EINVAL, "%s: neither a profile nor region probabilities asked for", who);
+    const int L = pb.variants[v].N;
+    if (!region_probs) n_regions = 0;
+    if (region_probs && n_regions < 1) return fail(ADX_EINVAL, "%s: region_probs without regions", who);
+    if (!unpaired_args_ok(L, max_len, profile != nullptr, n_regions, regions))
+        return fail(ADX_EINVAL, "%s: max_len %d outside [%d, %d], or a region outside [0, %d) or of length < 1", who,
+                    max_len, profile ? 1 : 0, L, L);
+    if (size_t(W) > SIZE_MAX / sizeof(double) / size_t(L) / size_t(std::max(max_len, 1)))
+        return fail(ADX_EINVAL, "%s: %d profiles of %d x %d overflow", who, W, max_len, L);
+    return pb.unpaired(dseqs, W, v, max_len, n_regions, regions, profile, region_probs, nullptr, energies);
+}
+
+extern "C" adx_status adx_unpaired_probs_batch(adx_ctx *c, int W, const char *seqs, int variant, int max_len,
+                                               int n_regions, const int *regions, double *profile,
+                                               double *region_probs, float *energies) {
+    if (!c || W <= 0 || !seqs) return fail(ADX_EINVAL, "adx_unpaired_probs_batch: bad argument");
+    Problem &pb = c->pb;
+    DevBuf<uint8_t> dseq;
+    if (adx_status su = upload_codes(seqs, size_t(W) * pb.Nraw, dseq, pb.stream)) return su;
+    return unpaired_probs(c, "adx_unpaired_probs_batch", dseq.p, W, variant, max_len, n_regions, regions, profile,
+                          region_probs, energies);
+}
+
+extern "C" adx_status adx_walkers_unpaired_probs(adx_ctx *c, int variant, int max_len, int n_regions,
+                                                 const int *regions, double *profile, double *region_probs,
+                                                 float *energies) {
+    if (!c) return fail(ADX_EINVAL, "adx_walkers_unpaired_probs: null argument");
+    if (c->pb.mode == ADX_FOLD_PF && c->W <= 0)
+        return fail(ADX_ESTATE, "adx_walkers_unpaired_probs before adx_walkers_init");
+    return unpaired_probs(c, "adx_walkers_unpaired_probs", c->cur_seq.p, c->W, variant, max_len, n_regions, regions,
+                          profile, region_probs, energies);
+}
+
+extern "C" adx_status adx_last_unpaired_ms(const adx_ctx *c, double *fill_ms, double *outside_ms) {
+    if (!c || !fill_ms || !outside_ms) return fail(ADX_EINVAL, "adx_last_unpaired_ms: null argument");
+    *fill_ms = c->pb.access_fill_ms;
+    *outside_ms = c->pb.access_outside_ms;
+    return ADX_OK;
+}
+
 // centroid and MEA structures of W device sequences for the (context, condition) unconstrained fold
 static adx_status ensemble_structures(adx_ctx *c, const char *who, const uint8_t *dseqs, int W, int condition,
                                       int context, double gamma, char *centroid, char *mea,

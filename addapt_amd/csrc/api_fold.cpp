@@ -255,6 +255,22 @@ extern "C" adx_status adx_fold_eval_structures(adx_fold *f, int convention, int 
     return pb.eval_structures(dseq.p, 1, 0, n, structures, true, energies, probs, status);
 }
 
+extern "C" adx_status adx_fold_unpaired_probs(adx_fold *f, int max_len, double *probs, double *pair_probs,
+                                              float *energy_kcal) {
+    if (!f || !probs) return fail(ADX_EINVAL, "adx_fold_unpaired_probs: null argument");
+    const int N = static_cast<int>(f->seq.size());
+    if (!unpaired_args_ok(N, max_len, true, 0, nullptr))
+        return fail(ADX_EINVAL, "adx_fold_unpaired_probs: max_len %d outside [1, %d]", max_len, N);
+    Problem pb;
+    // the default scale serves: pf_fill_kernel and pf_access_kernel sum in FP64
+    adx_status s = fold_problem(f, 0, pb);
+    if (s) return s;
+    DevBuf<uint8_t> dseq;
+    s = upload_codes(f->seq.data(), f->seq.size(), dseq, pb.stream);
+    if (s) return s;
+    return pb.unpaired(dseq.p, 1, 0, max_len, 0, nullptr, probs, nullptr, pair_probs, energy_kcal);
+}
+
 extern "C" adx_status adx_fold_bpp(adx_fold *f, int i, int j, double *prob) {
     if (!f || !prob) return fail(ADX_EINVAL, "adx_fold_bpp: null argument");
     const int N = static_cast<int>(f->seq.size());

@@ -69,6 +69,8 @@ struct Problem : DeviceStream {
     DevBuf<DevTables> dTE;       // struct_eval_kernel: energy-valued tables of a PF problem (an MFE problem's dT serves)
     DevBuf<EvalTab> dEval;       // and the convention's loop-length table (setup_core.hpp build_eval_tab)
     float eval_fill_ms = 0.f, eval_ms = 0.f;            // the last eval_structures() call, from HIP events
+    DevBuf<double> dAccess;      // pf_fill_kernel's tables, the adjoints and the run table of pf_access_kernel, one launch chunk
+    float access_fill_ms = 0.f, access_outside_ms = 0.f;   // the last unpaired() call, from HIP events
     size_t tab_slot = 0;
     bool state_on = false;   // set for MC launches only (not for adx_score_batch)
     std::unique_ptr<DevTables> hT;
@@ -505,6 +507,66 @@ struct Problem : DeviceStream {
         return ADX_OK;
     }
 
+    // Unpaired-region probabilities of W sequences (device codes) under variant v, to HOST
+    // buffers (each optional): profile[W][max_len][L], region_probs[W][n_regions] for the
+    // n_regions (first, length) pairs of `regions` (host), pair_probs[W][L][L], energies[W].
+    // pf_sample.hip's FP64 fill on the longer slices of pf_access.hip, then its outside
+    // pass; only what was asked for crosses to the host.  Every buffer is the call's own:
+    // no fold state is touched.  ADX_ACCESS_CHUNK=<n> (tests) bounds the sequences per
+    // launch; the results do not depend on it.
+    adx_status unpaired(const uint8_t *dseqs, int W, int v, int max_len, int n_regions, const int *regions,
+                        double *profile, double *region_probs, double *pair_probs, float *energies) {
+        const KArgs ka = kargs();
+        const size_t L = size_t(variants[v].N);
+        const size_t n_prof = profile ? size_t(max_len) * L : 0, n_reg = region_probs ? size_t(n_regions) : 0;
+        const size_t n_pair = pair_probs ? L * L : 0;
+        int per = pf_access_chunk(ka, W, n_prof + n_reg + n_pair);
+        if (const char *env = std::getenv("ADX_ACCESS_CHUNK"))
+            if (std::atoi(env) > 0) per = std::min(per, std::atoi(env));
+        const size_t slice = pf_access_slice_doubles(ka);
+        if (dAccess.n < size_t(per) * slice) HIP_TRY(dAccess.alloc(size_t(per) * slice));
+        DevBuf<double> dprof, dreg, dpair;
+        DevBuf<int> dregions;
+        DevBuf<float> de;
+        if (n_prof) HIP_TRY(dprof.alloc(size_t(per) * n_prof));
+        if (n_reg) {
+            HIP_TRY(dreg.alloc(size_t(per) * n_reg));
+            HIP_TRY(dregions.upload(regions, 2 * n_reg, stream));
+        }
+        if (n_pair) HIP_TRY(dpair.alloc(size_t(per) * n_pair));
+        HIP_TRY(de.alloc(W));
+        const AccessOut d{profile ? max_len : 0, int(n_reg), dregions.p, dprof.p, dreg.p, dpair.p};
+        Events ev;
+        if (adx_status se = ev.create(3)) return se;
+        access_fill_ms = access_outside_ms = 0.f;
+        for (int w0 = 0; w0 < W; w0 += per) {
+            const int n = std::min(per, W - w0);
+            HIP_TRY(hipEventRecord(ev[0], stream));
+            HIP_TRY(launch_pf_fill(ka, v, dseqs, w0, n, dAccess.p, de.p, stream, slice));
+            HIP_TRY(hipEventRecord(ev[1], stream));
+            HIP_TRY(launch_pf_access(ka, v, dseqs, w0, n, dAccess.p, d, stream));
+            HIP_TRY(hipEventRecord(ev[2], stream));
+            if (n_prof)
+                HIP_TRY(hipMemcpyAsync(profile + size_t(w0) * n_prof, dprof.p, sizeof(double) * n * n_prof,
+                                       hipMemcpyDeviceToHost, stream));
+            if (n_reg)
+                HIP_TRY(hipMemcpyAsync(region_probs + size_t(w0) * n_reg, dreg.p, sizeof(double) * n * n_reg,
+                                       hipMemcpyDeviceToHost, stream));
+            if (n_pair)
+                HIP_TRY(hipMemcpyAsync(pair_probs + size_t(w0) * n_pair, dpair.p, sizeof(double) * n * n_pair,
+                                       hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipStreamSynchronize(stream));   // the buffers are reused by the next chunk
+            float a = 0.f, b = 0.f;
+            HIP_TRY(hipEventElapsedTime(&a, ev[0], ev[1]));
+            HIP_TRY(hipEventElapsedTime(&b, ev[1], ev[2]));
+            access_fill_ms += a;
+            access_outside_ms += b;
+        }
+        if (energies) HIP_TRY(hipMemcpyAsync(energies, de.p, sizeof(float) * W, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        return ADX_OK;
+    }
+
     // the per-walker buffers a fold of W walkers writes (grow-only)
     adx_status prepare(int W) {
         adx_status so = ensure_ovf(W);
@@ -564,6 +626,16 @@ inline adx_status calibrate(Problem &pb, const std::vector<uint8_t> &codes) {
 }
 
 inline bool subopt_args_ok(double delta_kcal, int max_structs) { return delta_kcal >= 0.0 && max_structs >= 1; }   // NaN: no
+
+// max_len in [1, L] with a profile, 0 allowed without; every region inside [0, L), length >= 1
+inline bool unpaired_args_ok(int L, int max_len, bool with_profile, int n_regions, const int *regions) {
+    if (max_len < (with_profile ? 1 : 0) || max_len > L || n_regions < 0 || (n_regions > 0 && !regions)) return false;
+    for (int r = 0; r < n_regions; r++) {
+        const int first = regions[2 * r], len = regions[2 * r + 1];
+        if (first < 0 || len < 1 || first >= L || len > L - first) return false;
+    }
+    return true;
+}
 
 inline bool ensemble_args_ok(double gamma, const char *centroid, const char *mea, const adx_ensemble_stats *stats) {
     return std::isfinite(gamma) && gamma > 0.0 && (centroid || mea || stats);

@@ -59,51 +59,59 @@ enum TermKind : uint8_t { TK_STK = 0, TK_B1, TK_I11, TK_I12, TK_I21, TK_I22, TK_
 constexpr float MFE_BIG = 1.0e7f;
 constexpr float MFE_MARK = 3.0e7f;   // non-pairable cell mark of the MFE tables
 
-struct DevTables {         // exp(-E/kT) (PF) or E (MFE), FP32; pair type 0 rows are "impossible"
-    float stack[8][8];
-    float mmH[8][5][5];
-    float mmI[8][5][5];
-    float mm1n[8][5][5];
-    float mm23[8][5][5];
-    float mlstem[8][5][5];   // mismatchM * TermAU * MLintern (dangles = 2)
-    float ext[8][6][6];      // exterior stem; neighbour code 5 = absent
-    float termAU[8];
-    float int11[8][8][5][5];
-    float int21[8][8][5][5][5];
-    float int22[8][8][5][5][5][5];
+// F: the factors' type.  The engine's is float (DevTables, DevScaled); a host program may
+// stage the same tables in double (setup_core.hpp build_tables / build_scaled) and run a
+// per-lane header free of the factors' rounding (tests/cpp/pf_access_core_probe.cc)
+template <class F>
+struct DevTablesT {        // exp(-E/kT) (PF) or E (MFE); pair type 0 rows are "impossible"
+    F stack[8][8];
+    F mmH[8][5][5];
+    F mmI[8][5][5];
+    F mm1n[8][5][5];
+    F mm23[8][5][5];
+    F mlstem[8][5][5];   // mismatchM * TermAU * MLintern (dangles = 2)
+    F ext[8][6][6];      // exterior stem; neighbour code 5 = absent
+    F termAU[8];
+    F int11[8][8][5][5];
+    F int21[8][8][5][5][5];
+    F int22[8][8][5][5][5][5];
 };
 
-struct DevScaled {
-    float ctab[CT_SIZE];     // see CT_* (copied to LDS)
-    float fgen[FG_SIZE];     // generic interior factors
+template <class F>
+struct DevScaledT {
+    F ctab[CT_SIZE];     // see CT_* (copied to LDS)
+    F fgen[FG_SIZE];     // generic interior factors
     // MFE only (mfe_cells.hip): generic interior energy = il[u] + nin[|n1 - n2|]
-    float il[32];            // interior[u]
-    float nin[32];           // min(MAX_NINIO, k * ninio)
+    F il[32];            // interior[u]
+    F nin[32];           // min(MAX_NINIO, k * ninio)
     // MFE packed (pack_mfe16) only, per loop size u: il[u] + nin[k] (k = 0..5),
     // bulge[u], 1 x (u-1) -- the interior-loop blocks' uniform energy record
     uint32_t ku16[32][8];
     // interior term lists (see NS_MAX); *_cnt[umax] = terms with u <= umax
     uint8_t s_n1[NS_MAX], s_n2[NS_MAX], s_kind[NS_MAX];
-    float s_f[NS_MAX];       // constant factor (sigma power, bulge / 1xn length)
+    F s_f[NS_MAX];       // constant factor (sigma power, bulge / 1xn length)
     uint8_t g_n1[NG_MAX], g_u[NG_MAX];
-    float g_f[NG_MAX];
+    F g_f[NG_MAX];
     int s_cnt[32], g_cnt[32];
-    float sig[NMAX + 4];     // sigma^k
-    float hp[NMAX + 1];      // hairpin length factor * sigma^(u+2)
-    float pwml[NMAX + 1];    // (expMLbase * sigma)^t
-    float mlclosing;         // expMLclosing * sigma^2
-    float mlbase_sig;        // expMLbase * sigma
+    F sig[NMAX + 4];     // sigma^k
+    F hp[NMAX + 1];      // hairpin length factor * sigma^(u+2)
+    F pwml[NMAX + 1];    // (expMLbase * sigma)^t
+    F mlclosing;         // expMLclosing * sigma^2
+    F mlbase_sig;        // expMLbase * sigma
     int n_special;
     uint32_t sp_key[MAX_SPECIAL_HP];
-    float sp_val[MAX_SPECIAL_HP];   // exp(-E_special) * sigma^(u+2)
+    F sp_val[MAX_SPECIAL_HP];   // exp(-E_special) * sigma^(u+2)
     double log_sigma;
     double kT;               // kcal/mol
     // ligand motif (vrna_sc_add_hi_motif)
     int motif_len;
     uint8_t motif_code[MAX_MOTIF];
     int8_t motif_pt[MAX_MOTIF];     // partner offset or -1
-    float motif_extra;              // exp(-Eint)(exp(-bonus)-1) * sigma^L
+    F motif_extra;              // exp(-Eint)(exp(-bonus)-1) * sigma^L
 };
+using DevTables = DevTablesT<float>;   // FP32: what every kernel reads
+using DevScaled = DevScaledT<float>;
+
 
 // What struct_eval_kernel (struct_eval.hip) reads besides an energy-valued
 // DevTables (the MFE image, setup_core.hpp build_tables): the loop-length

@@ -93,10 +93,30 @@ struct SamplePlan {
 };
 size_t pf_sample_slice_doubles(const KArgs &ka);   // doubles of HBM scratch per sequence
 SamplePlan pf_sample_plan(const KArgs &ka, int L, int W, int n_samples);
+// slice_doubles: the stride between the sequences' slices (0: pf_sample_slice_doubles; the fill
+// writes that many doubles at the head of each)
 hipError_t launch_pf_fill(const KArgs &ka, int variant, const uint8_t *seqs, int w0, int n, double *scratch,
-                          float *energies, hipStream_t stream);
+                          float *energies, hipStream_t stream, size_t slice_doubles = 0);
 hipError_t launch_pf_sample(const KArgs &ka, int variant, const uint8_t *seqs, int w0, int n, double *scratch,
                             int k0, int nk, uint64_t seed, char *structures, int *flag, hipStream_t stream);
+
+// ---- pf_access.hip: unpaired-region probabilities P_u(i,j) (the FP64 outside pass over
+// the tables launch_pf_fill left for these n sequences in `scratch`, slices of
+// pf_access_slice_doubles).  Outputs are device buffers of one launch, indexed by the
+// sequence's position in it.
+struct AccessOut {
+    int max_len, n_regions;
+    const int *regions;     // [n_regions][2] first (0-based, folded coordinates), length
+    double *profile;        // [n][max_len][L]: row u-1, column i-1 = the window of length u at i (optional)
+    double *region_probs;   // [n][n_regions] (optional)
+    double *pair_probs;     // [n][L][L] symmetric (optional)
+};
+// doubles of HBM scratch per sequence: the fill's 3 cells + Nmax + 2, the adjoints'
+// 3 cells and the Nmax x Nmax run table, 8 (6 cells + Nmax^2 + Nmax + 2) bytes
+size_t pf_access_slice_doubles(const KArgs &ka);
+int pf_access_chunk(const KArgs &ka, int W, size_t out_doubles);   // sequences per launch: slices + outputs stay bounded
+hipError_t launch_pf_access(const KArgs &ka, int variant, const uint8_t *seqs, int w0, int n, double *scratch,
+                            const AccessOut &out, hipStream_t stream);
 
 // ---- struct_eval.hip: energies, probabilities and status bytes of given structures,
 // one wave per (sequence, structure) item.  Sequences w0 .. w0 + n of `seqs`, n_per

@@ -242,10 +242,11 @@ SamplePlan pf_sample_plan(const KArgs &ka, int L, int W, int n_samples) {
 }
 
 hipError_t launch_pf_fill(const KArgs &ka, int variant, const uint8_t *seqs, int w0, int n, double *scratch,
-                          float *energies, hipStream_t stream) {
+                          float *energies, hipStream_t stream, size_t slice_doubles) {
     if (ka.mode != 0 || variant < 0 || variant >= ka.n_variants || n < 1) return hipErrorInvalidValue;
+    if (slice_doubles != 0 && slice_doubles < pf_sample_slice_doubles(ka)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(pf_fill_kernel, dim3(n), dim3(PS_NT), 0, stream, ka, variant, seqs, w0, scratch,
-                       pf_sample_slice_doubles(ka), energies);
+                       slice_doubles ? slice_doubles : pf_sample_slice_doubles(ka), energies);
     return hipGetLastError();
 }
 

@@ -37,19 +37,24 @@ constexpr int PC_HAIRPIN = 0, PC_MOTIF = 1, PC_INT = 2;
 constexpr int PS_NSHAPES = (PS_MAXLOOP + 1) * (PS_MAXLOOP + 2) / 2;   // 496
 constexpr int PS_MAXCAND = 1024;   // >= 2 + 496 + NMAX, 2 NMAX: bounds every candidate loop
 
-// the sequence-side data of one (sequence, variant), in LDS
-struct PfSeqLds {
+// the sequence-side data of one (sequence, variant), in LDS; F: the factors' type
+// (dev_types.hpp DevTablesT: float in the kernels)
+template <class F>
+struct PfSeqLdsT {
     alignas(16) uint32_t spk[MAX_SPECIAL_HP];   // special-hairpin keys (fold_common.hpp special_hp)
-    float spv[MAX_SPECIAL_HP];
+    F spv[MAX_SPECIAL_HP];
     uint8_t S[PS_NP], up[PS_NP], ptn[PS_NP], enc[PS_NP], flg[PS_NP], mat[PS_NP];
     uint8_t mcode[MAX_MOTIF];
     int8_t mpt[MAX_MOTIF];
 };
 
-struct PfModel {
-    const DevTables *T;
-    const DevScaled *X;
-    const PfSeqLds &L;
+using PfSeqLds = PfSeqLdsT<float>;
+
+template <class F>
+struct PfModelT {
+    const DevTablesT<F> *T;
+    const DevScaledT<F> *X;
+    const PfSeqLdsT<F> &L;
     double *qb, *qm, *qm1;   // the sequence's scratch slice (diagonal-major cells)
     double *q5;              // [0, N]
     int N, mL;
@@ -76,7 +81,7 @@ struct PfModel {
 
     // exp(-E_IntLoop / kT) sigma^(n1 + n2 + 2) (oracle/fold.c E_int); t2 = type of the reversed inner pair (q,p)
     TR_FN double f_int(int n1, int n2, int t, int t2, int si1, int sj1, int sp1, int sq1) const {
-        const float *ct = X->ctab;
+        const F *ct = X->ctab;
         const int nl = n1 > n2 ? n1 : n2, ns = n1 > n2 ? n2 : n1;
         if (nl == 0) return double(ct[CT_FSM + 0]) * ct[CT_STK + t * 8 + t2];
         if (ns == 0) {
@@ -215,6 +220,7 @@ struct PfModel {
         return v;
     }
 };
+using PfModel = PfModelT<float>;
 
 }  // namespace
 }  // namespace adx

@@ -53,21 +53,24 @@ inline float boltz(double e_dcal) { return static_cast<float>(boltz_d(e_dcal)); 
 // Loop factor of energy e (dcal/mol) spanning k scaled nucleotides: the
 // Boltzmann factor exp(-e/kT) sigma^k (partition function) or the energy
 // itself (MFE; INF_E and above -> MFE_BIG).  dev_types.hpp "Fold modes".
+// FT: the tables' type (dev_types.hpp DevTablesT: float for the engine)
+template <class FT>
 struct Fac {
     bool mfe;
     double sigma;
-    float operator()(double e, int k = 0) const {
-        if (mfe) return e >= INF_E ? MFE_BIG : static_cast<float>(e);
-        return static_cast<float>(boltz_d(e) * std::pow(sigma, k));
+    FT operator()(double e, int k = 0) const {
+        if (mfe) return e >= INF_E ? FT(MFE_BIG) : static_cast<FT>(e);
+        return static_cast<FT>(boltz_d(e) * std::pow(sigma, k));
     }
-    float zero() const { return mfe ? MFE_BIG : 0.f; }
-    float one() const { return mfe ? 0.f : 1.f; }
+    FT zero() const { return mfe ? FT(MFE_BIG) : FT(0); }
+    FT one() const { return mfe ? FT(0) : FT(1); }
 };
 
-inline void build_tables(const EnergyParams &P, DevTables &T, bool mfe) {
-    const Fac F{mfe, 1.0};
-    float *flat = reinterpret_cast<float *>(&T);
-    for (size_t k = 0; k < sizeof(DevTables) / sizeof(float); k++) flat[k] = F.zero();
+template <class FT>
+inline void build_tables(const EnergyParams &P, DevTablesT<FT> &T, bool mfe) {
+    const Fac<FT> F{mfe, 1.0};
+    FT *flat = reinterpret_cast<FT *>(&T);
+    for (size_t k = 0; k < sizeof(DevTablesT<FT>) / sizeof(FT); k++) flat[k] = F.zero();
     for (int a = 1; a <= 7; a++) {
         for (int b = 1; b <= 7; b++) T.stack[a][b] = F(P.stack[a][b]);
         for (int x = 0; x < 5; x++)
@@ -147,29 +150,30 @@ inline adx_status prepare_motif(const EnergyParams &P, const Motif &m, double &e
     return ADX_OK;
 }
 
+template <class FT>
 inline void build_scaled(const EnergyParams &P, double sigma, const Motif &m, double eint,
-                         const std::vector<int> &mpt, DevScaled &X, bool mfe) {
+                         const std::vector<int> &mpt, DevScaledT<FT> &X, bool mfe) {
     std::memset(&X, 0, sizeof X);
-    const Fac F{mfe, sigma};
+    const Fac<FT> F{mfe, sigma};
     auto sp = [&](int k) { return std::pow(sigma, k); };
-    float *ct = X.ctab;
+    FT *ct = X.ctab;
     // code = rtype*25 + S[q+1]*5 + S[p-1] of an inner pair; mismatchI[type2][sq1][sp1]
     for (int code = 0; code < 200; code++) {
         const int t2 = code / 25, x = (code / 5) % 5, y = code % 5;
         if (mfe) {   // energies: the inverse factor is the negated mismatch
             const int mm = t2 ? P.mmI[t2][x][y] : 0;
-            ct[CT_INVMM + code] = t2 ? static_cast<float>(-mm) : MFE_BIG;
-            ct[CT_BUL + code] = t2 ? static_cast<float>(-mm + (t2 > 2 ? P.TermAU : 0)) : MFE_BIG;
-            ct[CT_ONEN + code] = t2 ? static_cast<float>(-mm + P.mm1nI[t2][x][y]) : MFE_BIG;
-            ct[CT_M23O + code] = t2 ? static_cast<float>(P.mm23I[t2][x][y]) : MFE_BIG;
+            ct[CT_INVMM + code] = t2 ? static_cast<FT>(-mm) : FT(MFE_BIG);
+            ct[CT_BUL + code] = t2 ? static_cast<FT>(-mm + (t2 > 2 ? P.TermAU : 0)) : FT(MFE_BIG);
+            ct[CT_ONEN + code] = t2 ? static_cast<FT>(-mm + P.mm1nI[t2][x][y]) : FT(MFE_BIG);
+            ct[CT_M23O + code] = t2 ? static_cast<FT>(P.mm23I[t2][x][y]) : FT(MFE_BIG);
             continue;
         }
         const double mm = t2 ? boltz_d(P.mmI[t2][x][y]) : 0.0;
         const double inv = (mm > 0.0) ? 1.0 / mm : 0.0;
-        ct[CT_INVMM + code] = static_cast<float>(inv);
-        ct[CT_BUL + code] = static_cast<float>(inv * (t2 ? boltz_d(t2 > 2 ? P.TermAU : 0) : 0.0));
-        ct[CT_ONEN + code] = static_cast<float>(inv * (t2 ? boltz_d(P.mm1nI[t2][x][y]) : 0.0));
-        ct[CT_M23O + code] = static_cast<float>(t2 ? boltz_d(P.mm23I[t2][x][y]) : 0.0);
+        ct[CT_INVMM + code] = static_cast<FT>(inv);
+        ct[CT_BUL + code] = static_cast<FT>(inv * (t2 ? boltz_d(t2 > 2 ? P.TermAU : 0) : 0.0));
+        ct[CT_ONEN + code] = static_cast<FT>(inv * (t2 ? boltz_d(P.mm1nI[t2][x][y]) : 0.0));
+        ct[CT_M23O + code] = static_cast<FT>(t2 ? boltz_d(P.mm23I[t2][x][y]) : 0.0);
     }
     for (int a = 0; a < 8; a++)
         for (int b = 0; b < 8; b++) ct[CT_STK + a * 8 + b] = (a && b) ? F(P.stack[a][b]) : F.zero();
@@ -197,12 +201,12 @@ inline void build_scaled(const EnergyParams &P, double sigma, const Motif &m, do
                 n2 >= 2 ? F(P.interior[u] + std::min(P.maxninio, std::abs(n1 - n2) * P.ninio), u + 2) : F.zero();
         }
     for (int k = 0; k < 32; k++) {
-        X.il[k] = (mfe && k <= MAXLOOP) ? static_cast<float>(P.interior[k]) : 0.f;
-        X.nin[k] = mfe ? static_cast<float>(std::min(P.maxninio, k * P.ninio)) : 0.f;
+        X.il[k] = (mfe && k <= MAXLOOP) ? static_cast<FT>(P.interior[k]) : FT(0);
+        X.nin[k] = mfe ? static_cast<FT>(std::min(P.maxninio, k * P.ninio)) : FT(0);
     }
     // term lists ordered by u (dev_types.hpp NS_MAX)
     int ns = 0, ng = 0;
-    auto addS = [&](int kind, int n1, int n2, float f) {
+    auto addS = [&](int kind, int n1, int n2, FT f) {
         X.s_kind[ns] = static_cast<uint8_t>(kind);
         X.s_n1[ns] = static_cast<uint8_t>(n1);
         X.s_n2[ns] = static_cast<uint8_t>(n2);
@@ -241,7 +245,7 @@ inline void build_scaled(const EnergyParams &P, double sigma, const Motif &m, do
     }
     const double mlb = boltz_d(P.MLbase);
     for (int t = 0; t <= NMAX; t++)
-        X.pwml[t] = mfe ? static_cast<float>(t * P.MLbase) : static_cast<float>(std::pow(mlb * sigma, t));
+        X.pwml[t] = mfe ? static_cast<FT>(t * P.MLbase) : static_cast<FT>(std::pow(mlb * sigma, t));
     X.mlclosing = F(P.MLclosing, 2);
     X.mlbase_sig = F(P.MLbase, 1);
     int nsp = 0;
@@ -271,10 +275,10 @@ inline void build_scaled(const EnergyParams &P, double sigma, const Motif &m, do
         const bool replace = m.mode == ADX_MOTIF_REPLACE || (m.mode == ADX_MOTIF_AUTO && mfe);
         const double beff = replace ? m.energy_kcal - eint : m.energy_kcal;
         if (mfe) {   // min-plus image of the extra term: the formed motif's energy, rounded once to dcal
-            X.motif_extra = static_cast<float>(std::lround(100.0 * (eint + beff)));
+            X.motif_extra = static_cast<FT>(std::lround(100.0 * (eint + beff)));
         } else {
             const double extra = boltz_d(eint * 100.0) * (boltz_d(beff * 100.0) - 1.0) * sp(L);
-            X.motif_extra = static_cast<float>(extra);
+            X.motif_extra = static_cast<FT>(extra);
         }
     }
 }

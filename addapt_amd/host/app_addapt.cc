@@ -6,6 +6,7 @@
 //                      [--reference-loop] [--picks <path>] [--pick-window <steps>|auto]
 //                      [--autocorr <path>] [--autocorr-lag <steps>] [--autocorr-discard <steps>]
 //                      [--eval <path> --eval-structure <db>[,<db>...]]
+//                      [--access <path> --access-region <first>-<last>[,...] [--access-len <u>]]
 //                      [--designs <path>] [--design-radius <mutations>] [--max-designs <num>]
 #include <algorithm>
 #include <cmath>
@@ -82,6 +83,15 @@ static const char USAGE[] =
     "    loop above 30, or-ed).  A '#' line gives the device time of the last call.\n"
     "  --eval-structure <db>[,<db>...]\n"
     "    The target structures, dot-bracket, of the (context-padded) folded length.\n"
+    "  --access <path>\n"
+    "    With --walkers and --access-region: the probability that each region is all\n"
+    "    unpaired (RNAplfold -u's accessibility) on every walker's final sequence, on\n"
+    "    the GPU: one row per walker, unconstrained (context, condition) fold and\n"
+    "    region.  A '#' line gives the device time of the last call.\n"
+    "  --access-region <first>-<last>[,<first>-<last>...]\n"
+    "    The regions, 1-based and inclusive, in the (context-padded) folded coordinates.\n"
+    "  --access-len <u>\n"
+    "    Also one row for every window of up to u bases: the accessibility profile.\n"
     "  --gpu <id>                             [default: 0]\n"
     "  --params <file>  Energy parameters (ViennaRNA 2.0 format).\n"
     "  --reference-loop  Run the reference's single-walker loop (one GPU fold call\n"
@@ -177,10 +187,26 @@ static void write_evals(const std::string &path, const BatchResult &res, const s
     std::fclose(f);
 }
 
+// The accessibility of the regions (and windows) on the final walkers of a batched run.
+static void write_access(const std::string &path, const BatchResult &res, size_t n_regions, int access_len,
+                         const std::vector<uint32_t> &seeds) {
+    FILE *f = std::fopen(path.c_str(), "w");
+    if (!f) throw std::string("couldn't open '" + path + "' for writing");
+    std::fprintf(f, "# Num Regions: %zu\n# Profile Length: %d\n# Last Access ms: fill %.3f outside %.3f\n", n_regions,
+                 access_len, res.access_fill_ms, res.access_outside_ms);
+    std::fprintf(f, "walker\tseed\tcontext\tcondition\tfirst\tlast\tunpaired_probability\n");
+    for (auto &x : res.access)
+        std::fprintf(f, "%d\t%u\t%d\t%s\t%d\t%d\t%.17g\n", x.walker, seeds[size_t(x.walker)], x.context,
+                     x.condition ? "holo" : "apo", x.first + 1, x.first + x.length, x.prob);
+    std::fclose(f);
+}
+
 int main(int argc, char **argv) {
     std::vector<std::string> configs;
-    std::string temp, out = "traj.tsv", params, picks, autocorr, designs, evals;
+    std::string temp, out = "traj.tsv", params, picks, autocorr, designs, evals, access;
     std::vector<std::string> targets;
+    std::vector<std::pair<int, int>> regions;   // (first 0-based, length)
+    int access_len = 0;
     int num = 100, interval = 1, walkers = 1, gpu = 0, pick_window = 500, autocorr_lag = 500, autocorr_discard = 100;
     int design_radius = 3, max_designs = 100;
     bool auto_window = false;
@@ -213,6 +239,20 @@ int main(int argc, char **argv) {
             else if (a == "--designs") designs = val("--designs");
             else if (a == "--design-radius") design_radius = std::stoi(val("--design-radius"));
             else if (a == "--max-designs") max_designs = std::stoi(val("--max-designs"));
+            else if (a == "--access") access = val("--access");
+            else if (a == "--access-len") access_len = std::stoi(val("--access-len"));
+            else if (a == "--access-region") {
+                std::string v = val("--access-region"), t;
+                for (char ch : v + ",") {
+                    if (ch != ',') { t.push_back(ch); continue; }
+                    const size_t dash = t.find('-');
+                    if (dash == std::string::npos || dash == 0) throw std::string("--access-region wants <first>-<last>, not '" + t + "'");
+                    const int first = std::stoi(t.substr(0, dash)), last = std::stoi(t.substr(dash + 1));
+                    if (first < 1 || last < first) throw std::string("--access-region '" + t + "': 1 <= first <= last");
+                    regions.push_back({first - 1, last - first + 1});
+                    t.clear();
+                }
+            }
             else if (a == "--eval") evals = val("--eval");
             else if (a == "--eval-structure") {
                 std::string v = val("--eval-structure"), t;
@@ -236,6 +276,10 @@ int main(int argc, char **argv) {
         if (!designs.empty() && walkers <= 1) throw std::string("--designs needs --walkers <W> with W > 1");
         if (!evals.empty() && walkers <= 1) throw std::string("--eval needs --walkers <W> with W > 1");
         if (evals.empty() != targets.empty()) throw std::string("--eval <path> and --eval-structure <db>[,<db>...] go together");
+        if (!access.empty() && walkers <= 1) throw std::string("--access needs --walkers <W> with W > 1");
+        if (access.empty() != regions.empty()) throw std::string("--access <path> and --access-region <first>-<last>[,...] go together");
+        if (access_len != 0 && access.empty()) throw std::string("--access-len goes with --access");
+        if (access_len < 0) throw std::string("--access-len must not be negative");
         const bool picking = !picks.empty() || !designs.empty();
         if (picking && !auto_window && pick_window < 1) throw std::string("--pick-window must be at least 1");
         if (!designs.empty() && design_radius < 0) throw std::string("--design-radius must not be negative");
@@ -266,6 +310,8 @@ int main(int argc, char **argv) {
             opt.autocorr_lag = correlating ? autocorr_lag : 0;
             opt.autocorr_discard = correlating ? autocorr_discard : 0;
             opt.eval_structures = targets;
+            opt.access_regions = regions;
+            opt.access_len = access_len;
             auto res = mc->apply_batch(device, seeds, gpu, opt);
             FILE *f = std::fopen(out.c_str(), "w");
             if (!f) throw std::string("couldn't open '" + out + "' for writing");
@@ -282,6 +328,7 @@ int main(int argc, char **argv) {
             if (!autocorr.empty()) write_autocorr(autocorr, res.autocorr);
             if (!designs.empty()) write_designs(designs, res, design_radius, seeds);
             if (!evals.empty()) write_evals(evals, res, targets, seeds);
+            if (!access.empty()) write_access(access, res, regions.size(), access_len, seeds);
             return 0;
         }
         *mc += std::make_shared<ProgressReporter>();

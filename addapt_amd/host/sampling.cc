@@ -279,6 +279,16 @@ BatchResult MonteCarlo::apply_batch(DevicePtr device, const std::vector<uint32_t
         for (size_t c = 0; c < e.ctx.size(); c++) fits = fits || t.size() == folded_length(int(c));
         if (!fits) throw string("apply_batch: target structure '" + t + "' has the folded length of no context");
     }
+    if (opt.access_len != 0 && opt.access_regions.empty()) throw string("apply_batch: access_len goes with access_regions");
+    for (auto &r : opt.access_regions) {   // inside every fold they are asked of
+        size_t shortest = folded_length(-1);
+        for (size_t c = 0; c < e.ctx.size(); c++) shortest = c == 0 ? folded_length(0) : std::min(shortest, folded_length(int(c)));
+        if (r.first < 0 || r.second < 1 || size_t(r.first) + size_t(r.second) > shortest)
+            throw string("apply_batch: access region (" + std::to_string(r.first) + ", " + std::to_string(r.second) +
+                         ") leaves the folded sequence of a context");
+        if (opt.access_len < 0 || size_t(opt.access_len) > shortest)
+            throw string("apply_batch: access_len " + std::to_string(opt.access_len) + " outside the folded sequence");
+    }
     adx_ctx *raw = nullptr;
     gpu::check(adx_ctx_create(&e.d, &raw));
     gpu::CtxPtr ctx(raw);
@@ -404,6 +414,36 @@ BatchResult MonteCarlo::apply_batch(DevicePtr device, const std::vector<uint32_t
         }
         gpu::check(adx_last_eval_ms(ctx.get(), &out.eval_fill_ms, &out.eval_ms));
         for (auto &rows : per) out.evals.insert(out.evals.end(), rows.begin(), rows.end());
+    }
+    if (!opt.access_regions.empty()) {
+        adx_info info;
+        gpu::check(adx_ctx_info(ctx.get(), &info));
+        const size_t R = opt.access_regions.size(), U = size_t(opt.access_len);
+        std::vector<int> reg;
+        for (auto &r : opt.access_regions) {
+            reg.push_back(r.first);
+            reg.push_back(r.second);
+        }
+        std::vector<std::vector<RegionAccess>> per;   // per walker, folds in variant order
+        per.resize(size_t(W));
+        for (int v = 0; v < info.n_variants; v++) {
+            int c = -1, cond = 0, mac = -1;
+            gpu::check(adx_variant_desc(ctx.get(), v, &c, &cond, &mac));
+            if (mac >= 0) continue;   // the unconstrained folds only
+            const size_t L = folded_length(c);
+            std::vector<double> rp(size_t(W) * R), prof(size_t(W) * U * L);
+            gpu::check(adx_walkers_unpaired_probs(ctx.get(), v, int(U), int(R), reg.data(), U ? prof.data() : nullptr,
+                                                  rp.data(), nullptr));
+            for (int w = 0; w < W; w++) {
+                for (size_t k = 0; k < R; k++)
+                    per[size_t(w)].push_back(RegionAccess{w, c, cond, reg[2 * k], reg[2 * k + 1], rp[size_t(w) * R + k]});
+                for (size_t u = 1; u <= U; u++)
+                    for (size_t i = 0; i + u <= L; i++)
+                        per[size_t(w)].push_back(RegionAccess{w, c, cond, int(i), int(u), prof[(size_t(w) * U + u - 1) * L + i]});
+            }
+        }
+        gpu::check(adx_last_unpaired_ms(ctx.get(), &out.access_fill_ms, &out.access_outside_ms));
+        for (auto &rows : per) out.access.insert(out.access.end(), rows.begin(), rows.end());
     }
     for (int w = 0; w < W; w++) {
         out[w].device = device->copy();

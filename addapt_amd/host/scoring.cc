@@ -133,6 +133,23 @@ std::pair<std::vector<string>, double> GpuRnaFold::sample_structures(int n, uint
     return {out, double(e)};
 }
 
+// RNAplfold -u on the fold compound macrostate_prob builds
+UnpairedProbs GpuRnaFold::unpaired_probs(int max_len, string constraint) const {
+    adx_fold *raw = nullptr;
+    gpu::check(adx_fold_create(gpu::params(), seq_.c_str(), 0, gpu_, &raw));
+    gpu::FoldPtr f(raw);
+    if (aptamer_)
+        gpu::check(adx_fold_add_motif(f.get(), aptamer_->seq().c_str(), aptamer_->fold().c_str(),
+                                      kT() * std::log(aptamer_->affinity() / 1e6)));
+    if (!constraint.empty()) gpu::check(adx_fold_add_constraint(f.get(), constraint.c_str()));
+    UnpairedProbs out{max_len, std::vector<double>(size_t(max_len > 0 ? max_len : 0) * seq_.size() + 1), 0.0};
+    float e = 0.f;
+    gpu::check(adx_fold_unpaired_probs(f.get(), max_len, out.probs.data(), nullptr, &e));
+    out.probs.resize(size_t(max_len) * seq_.size());
+    out.energy = double(e);
+    return out;
+}
+
 // RNAeval on the fold compound macrostate_prob builds
 std::vector<StructureEval> GpuRnaFold::eval_structures(const std::vector<string> &structures, string constraint,
                                                        bool mfe) const {

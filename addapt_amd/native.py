@@ -88,6 +88,7 @@ EXPORTS = [
     "adx_fold_sample_structures", "adx_sample_structures_batch", "adx_walkers_sample_structures",
     "adx_last_sample_ms",
     "adx_fold_eval_structures", "adx_eval_structures_batch", "adx_walkers_eval_structures", "adx_last_eval_ms",
+    "adx_fold_unpaired_probs", "adx_unpaired_probs_batch", "adx_walkers_unpaired_probs", "adx_last_unpaired_ms",
     "adx_fold_ensemble_structures", "adx_ensemble_structures_batch", "adx_walkers_ensemble_structures",
     "adx_last_ensemble_ms",
     "adx_pick_scores", "adx_record_begin", "adx_record_end", "adx_record_picks", "adx_last_pick_ms",
@@ -145,6 +146,13 @@ def lib():
         L.adx_walkers_eval_structures.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_double),
                                                   C.POINTER(C.c_double), C.POINTER(C.c_uint8)]
         L.adx_last_eval_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        unpaired_out = [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                        C.POINTER(C.c_float)]
+        L.adx_fold_unpaired_probs.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                              C.POINTER(C.c_float)]
+        L.adx_unpaired_probs_batch.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_int] + unpaired_out
+        L.adx_walkers_unpaired_probs.argtypes = [C.c_void_p, C.c_int] + unpaired_out
+        L.adx_last_unpaired_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.adx_fold_ensemble_structures.argtypes = [C.c_void_p, C.c_double, C.c_char_p, C.c_char_p,
                                                    C.POINTER(EnsembleStats)]
         L.adx_ensemble_structures_batch.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_double,
@@ -233,6 +241,21 @@ def _eval_structures(n_seqs, n_per, L, structures, with_probs, call):
                 st.ctypes.data_as(C.POINTER(C.c_uint8))))
     shape = (n_seqs, n_per)
     return e.reshape(shape), p.reshape(shape) if with_probs else None, st.reshape(shape)
+
+
+def _unpaired(W, L, max_len, regions, call):
+    """(profile (W, max_len, L) or None, region probabilities (W, n_regions) or None, float32
+    energies) of an unpaired-probs call; regions: (first, length) pairs, first 0-based."""
+    reg = np.ascontiguousarray(regions if regions is not None else [], np.int32).reshape(-1, 2)
+    R = len(reg)
+    prof = np.zeros((W, max(max_len, 0), L), np.float64) if max_len != 0 else None
+    rp = np.zeros((W, R), np.float64) if regions is not None else None
+    e = np.zeros(max(W, 1), np.float32)
+    dp = C.POINTER(C.c_double)
+    _check(call(max_len, R, reg.ctypes.data_as(C.POINTER(C.c_int)) if R else None,
+                prof.ctypes.data_as(dp) if prof is not None else None,
+                rp.ctypes.data_as(dp) if rp is not None else None, e.ctypes.data_as(C.POINTER(C.c_float))))
+    return prof, rp, e[:W]
 
 
 def kT():
@@ -449,6 +472,21 @@ class Fold:
                                     lambda s, en, pr, sb: lib().adx_fold_eval_structures(self.ptr, conv, n, s, en, pr, sb))
         return e[0], p[0] if with_probs else None, st[0]
 
+    def unpaired_probs(self, max_len, pair_probs=False):
+        """(P_u (max_len, N), pair probabilities (N, N) or None, ensemble energy kcal/mol), float64:
+        RNAplfold -u's accessibility.  P_u[u - 1, i - 1] is the probability that the u bases
+        from i (1-based) on are all unpaired, motif and constraint honoured; 0 past N - u and
+        where the constraint forces a base of the window to pair, NaN everywhere when the
+        constraint admits no structure."""
+        ml = max(max_len, 0)
+        p = np.zeros((ml, self.N), np.float64)
+        pp = np.zeros((self.N, self.N), np.float64) if pair_probs else None
+        g = C.c_float()
+        dp = C.POINTER(C.c_double)
+        _check(lib().adx_fold_unpaired_probs(self.ptr, max_len, p.ctypes.data_as(dp),
+                                             pp.ctypes.data_as(dp) if pair_probs else None, C.byref(g)))
+        return p, pp, g.value
+
     def ensemble_structures(self, gamma=1.0):
         """(centroid, MEA structure, EnsembleStats) of the ensemble: RNAfold -p --MEA's
         lines after the MFE one.  The statistics are NaN when the constraint admits nothing."""
@@ -663,6 +701,28 @@ class Engine:
         """(fill ms, eval ms) of the last eval_structures / walker_eval_structures call, from HIP events."""
         a, b = C.c_double(), C.c_double()
         _check(lib().adx_last_eval_ms(self.ptr, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def unpaired_probs(self, seqs, variant, max_len=0, regions=None):
+        """(profile (W, max_len, L) or None when max_len is 0, region probabilities (W, n) or
+        None, float32 ensemble energies) of `seqs` in fold variant `variant` (fold_mode="pf"
+        engines): the probability that a window is all unpaired, float64.  profile[w, u - 1, i]
+        is the window of u bases from 0-based i on; regions are (first, length) pairs, first
+        0-based, both in the variant's folded (context-padded) coordinates."""
+        W = len(seqs)
+        seqbuf = b"".join(_b(s) for s in seqs)
+        return _unpaired(W, self._variant_length(variant), max_len, regions,
+                         lambda *a: lib().adx_unpaired_probs_batch(self.ptr, W, seqbuf, variant, *a))
+
+    def walker_unpaired_probs(self, variant, max_len=0, regions=None):
+        """The same for the walkers' current sequences, read on the device."""
+        return _unpaired(max(self.W, 0), self._variant_length(variant), max_len, regions,
+                         lambda *a: lib().adx_walkers_unpaired_probs(self.ptr, variant, *a))
+
+    def last_unpaired_ms(self):
+        """(fill ms, outside ms) of the last unpaired_probs / walker_unpaired_probs call, from HIP events."""
+        a, b = C.c_double(), C.c_double()
+        _check(lib().adx_last_unpaired_ms(self.ptr, C.byref(a), C.byref(b)))
         return a.value, b.value
 
     def _ensemble(self, W, condition, context, with_probs, call):

@@ -202,6 +202,16 @@ struct TargetEval {
     int status;          ///< 0: a member, else ADX_EVAL_* bits (addapt_gpu.h)
 };
 
+/// the probability that a window of one walker's final sequence is all unpaired
+/// (adx_walkers_unpaired_probs) in one unconstrained (context, condition) fold
+struct RegionAccess {
+    int walker;
+    int context;         ///< the score function's context (-1: none)
+    int condition;       ///< 0 apo, 1 holo
+    int first, length;   ///< the window, first 0-based, in the fold's (context-padded) coordinates
+    double prob;         ///< NaN: the fold's ensemble is empty
+};
+
 /// the walkers' results; with a pick window also how often A, C, G, U stand at
 /// each position over all walkers' picks (base_counts[4 * position + base])
 struct BatchResult : std::vector<WalkerResult> {
@@ -212,6 +222,9 @@ struct BatchResult : std::vector<WalkerResult> {
     int64_t n_picks = 0;               ///< and the number of picks the designs were selected from
     double eval_fill_ms = 0.0, eval_ms = 0.0;   ///< device time of the last eval call (adx_last_eval_ms): FP64 fill, kernel
     std::vector<TargetEval> evals;     ///< filled with BatchOptions::eval_structures: walker-major, then target, then fold
+    double access_fill_ms = 0.0, access_outside_ms = 0.0;   ///< device time of the last access call (adx_last_unpaired_ms)
+    std::vector<RegionAccess> access;  ///< filled with BatchOptions::access_regions: walker-major, then fold, then the
+                                       ///< regions and, with access_len > 0, every window of up to that length
 };
 
 /// what a batched run does besides stepping
@@ -226,6 +239,10 @@ struct BatchOptions {
     int max_designs = 100;      ///< at most this many designs
     std::vector<std::string> eval_structures;   ///< target dot-brackets priced on every walker's final sequence, in each
                                                 ///< unconstrained (context, condition) fold of their (context-padded) length
+    std::vector<std::pair<int, int>> access_regions;   ///< (first, length), first 0-based, in folded coordinates: the probability
+                                                       ///< that each is all unpaired on every walker's final sequence, in each
+                                                       ///< unconstrained (context, condition) fold
+    int access_len = 0;         ///< > 0: with access_regions also every window of up to this many bases
 };
 
 class MonteCarlo {

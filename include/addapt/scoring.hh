@@ -62,6 +62,15 @@ struct StructureEval {
     int status;      ///< 0: a member of the ensemble, else ADX_EVAL_* bits (addapt_gpu.h)
 };
 
+/// Unpaired-region probabilities of one sequence (GpuRnaFold::unpaired_probs).
+struct UnpairedProbs {
+    int max_len;                 ///< the longest window
+    std::vector<double> probs;   ///< [max_len][L]: row u-1, column i the window of u bases from 0-based i on; 0 past L-u
+    double energy;               ///< the ensemble energy, kcal/mol; +inf (and every window NaN) when the constraint admits nothing
+    /// the probability that the `length` bases from 0-based `first` on are all unpaired
+    double at(int first, int length) const { return probs[size_t(length - 1) * (probs.size() / size_t(max_len)) + size_t(first)]; }
+};
+
 /// Zuker suboptimal structures of one sequence (GpuRnaFold::subopt_structures).
 struct SuboptStructures {
     double mfe;                              ///< kcal/mol; +inf when the constraint admits nothing
@@ -88,6 +97,10 @@ public:
     /// optional hard constraint, and the ensemble energy in kcal/mol; the aptamer
     /// motif counts as in macrostate_prob.  Sample k under `seed` does not depend on n.
     std::pair<std::vector<string>, double> sample_structures(int n, uint64_t seed, string constraint = "") const;
+    /// RNAplfold -u's accessibility: the probability that a window is all unpaired, for
+    /// every window of up to max_len bases, under an optional hard constraint; the
+    /// aptamer motif counts as in macrostate_prob.  An FP64 outside pass on the GPU.
+    UnpairedProbs unpaired_probs(int max_len, string constraint = "") const;
     /// The centroid and the MEA structure (weight gamma, RNAfold's default 1) of the
     /// ensemble under an optional hard constraint, with the three statistics; the
     /// aptamer motif counts as in macrostate_prob.  Both all '.' and the statistics

@@ -151,6 +151,25 @@ adx_status adx_fold_sample_structures(adx_fold *f, int n_samples, uint64_t seed,
 #define ADX_EVAL_BIGLOOP 8
 adx_status adx_fold_eval_structures(adx_fold *f, int convention, int n, const char *structures,
                                     double *energies, double *probs, uint8_t *status);
+/* Unpaired-region probabilities (RNAplfold -u / RNAup's accessibility) of the
+ * ensemble the compound describes (motif, constraint), FP64, from an outside
+ * pass over the FP64 fill on the GPU.  With L = strlen(seq) and Z the
+ * ensemble's partition function, for every window [i..j], 1 <= i <= j <= L,
+ * j - i + 1 <= max_len:
+ *   P_u(i, j) = Z(the ensemble restricted to structures with i..j all unpaired) / Z
+ * which is what two partition functions give: the compound's own, and one with
+ * 'x' merged into the constraint over the window.
+ *   probs       max_len * L doubles: row u-1, column i-1 holds the window of
+ *               length u starting at i (1-based); columns past L-u are 0
+ *   pair_probs  optional (NULL): L * L doubles, symmetric, the pair probabilities
+ *   energy_kcal optional: the ensemble energy (+inf: the empty ensemble)
+ * A window is exactly 0 where the constraint forces one of its bases to pair
+ * ('|', '<', '>', '(', ')'); every entry of probs is NaN when the constraint
+ * admits no structure at all (pair_probs too); sequences too short to pair
+ * (L < 5) give 1 everywhere.  max_len outside [1, L]: ADX_EINVAL.  Equal
+ * inputs give equal bytes. */
+adx_status adx_fold_unpaired_probs(adx_fold *f, int max_len, double *probs, double *pair_probs,
+                                   float *energy_kcal);
 /* What RNAfold -p --MEA prints after the MFE line, for the ensemble the compound
  * describes (motif, constraint), from its pair probabilities P on the GPU:
  *   centroid       the pairs with P > 1/2 (taken in ascending (i, j); a pair that
@@ -461,6 +480,36 @@ adx_status adx_walkers_eval_structures(adx_ctx *ctx, int variant, int n_structs,
 /* Device time (ms, HIP events) of the context's last eval-structures call: the
  * FP64 fill (0 without probs) and the eval kernel. */
 adx_status adx_last_eval_ms(const adx_ctx *ctx, double *fill_ms, double *eval_ms);
+
+/* Unpaired-region probabilities (adx_fold_unpaired_probs) of n_seqs sequences
+ * (n_seqs*N chars) under variant v (adx_variant_desc), with the variant's
+ * context padding, constraint and motif; L = the variant's folded,
+ * context-padded length, the coordinates of the sampled structures.
+ *   profile       n_seqs * max_len * L doubles (per sequence the layout of
+ *                 adx_fold_unpaired_probs), or NULL
+ *   regions       n_regions (first, length) pairs, first 0-based in the folded
+ *                 coordinates; a region may be longer than max_len
+ *   region_probs  n_seqs * n_regions doubles, sequence-major, or NULL; an entry
+ *                 equals the profile's entry of the same window, bit for bit
+ *   energies      n_seqs ensemble energies, optional
+ * profile and region_probs may not both be NULL; with profile NULL max_len may
+ * be 0.  ADX_EUNSUPPORTED on an MFE context; ADX_EINVAL for a bad variant,
+ * max_len outside [1, L] (0 only without a profile), a region outside the
+ * sequence or of length < 1.  Walker state, the stored tables and the next
+ * step's results are not touched. */
+adx_status adx_unpaired_probs_batch(adx_ctx *ctx, int n_seqs, const char *seqs, int variant, int max_len,
+                                    int n_regions, const int *regions, double *profile, double *region_probs,
+                                    float *energies);
+
+/* The same on the walkers' current sequences, read on the device: only the
+ * requested numbers cross to the host (with regions alone W * n_regions
+ * doubles).  Outputs are walker-major (ADX_ESTATE before adx_walkers_init). */
+adx_status adx_walkers_unpaired_probs(adx_ctx *ctx, int variant, int max_len, int n_regions, const int *regions,
+                                      double *profile, double *region_probs, float *energies);
+
+/* Device time (ms, HIP events) of the context's last unpaired-probs call: the
+ * FP64 inside fill and the outside pass with its window sums. */
+adx_status adx_last_unpaired_ms(const adx_ctx *ctx, double *fill_ms, double *outside_ms);
 
 /* ------------------------------------------------------------------------
  * Picking each trajectory's best steps on the device (what the reference's
